@@ -10,6 +10,10 @@ actor/critic/replay-value losses, backward, (all-reduce), AGC + LaProp. Each ste
 
 Run: python bench.py [--gpus N --steps K --warmup W]; N > 1 under torch.distributed.run (weak scaling: B=16/GPU,
 gradient all-reduce over RCCL). Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line. --full adds everything else the line
+can carry: the live roofline probes and phase rooflines, the WM-loss parity legs and the CPU baseline (--no-roofline /
+--no-cpu-baseline drop either half again). --dump-outputs DIR writes what the last timed step returned as .npy files.
 """
 from __future__ import annotations
 
@@ -714,6 +718,40 @@ def phase_rooflines(agent, cfg, cfg_name, ms_update, table=None, reps=10, census
     return out
 
 
+DUMP_ARRAY_BYTES = 24 << 20  # per dumped array; two large arrays + the scalar metrics stay under 64 MB in all
+
+
+class _LastPosterior:
+    """Keeps the posterior latents of the latest update: `Dreamer.update` hands them to `Buffer.update` (the replay
+    write-back) and returns only the metrics, so the dump reads them where the replay buffer receives them."""
+
+    def __init__(self, buf):
+        self.stoch = self.deter = None
+        self._write_back = buf.update
+        buf.update = self
+
+    def __call__(self, index, stoch, deter):
+        self.stoch, self.deter = stoch, deter
+        return self._write_back(index, stoch, deter)
+
+
+def dump_outputs(path, mets, post):
+    """What the last timed `agent.update(buf)` handed back, one float32 `<name>.npy` each: every metric of the returned
+    dict (`/` in its name written as `.`) and the posterior (post_stoch, post_deter) it wrote to the replay buffer. An
+    array above DUMP_ARRAY_BYTES is cut to a fixed sample of its flattened elements (indices from default_rng(0))."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k.replace("/", "."): (v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.float32(v))
+              for k, v in mets.items()}
+    arrays["post_stoch"] = post.stoch.detach().float().cpu().numpy()
+    arrays["post_deter"] = post.deter.detach().float().cpu().numpy()
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, DUMP_ARRAY_BYTES // 4))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -729,7 +767,15 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL); gloo only to rehearse N ranks on one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: roofline probes and phase rooflines, the "
+                         "WM-loss parity legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (metrics, posterior latents) to "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
+    roofline = args.full and not args.no_roofline
+    cpu_legs = args.full and not args.no_cpu_baseline
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -769,9 +815,9 @@ def main():
     # roofline probes on the update's largest launch shapes: LaunchProbes see their launch during the warm-up (eager
     # update or graph capture) and re-time that exact launch with HIP events on its stream after the timed steps;
     # the imagination / scan kernels are re-issued through their step entry points
-    specs = None if args.no_roofline else probe_specs(agent, cfg, K)
+    specs = probe_specs(agent, cfg, K) if roofline else None
     census = None
-    if not args.no_roofline and args.warmup > 0:  # FLOP by arithmetic of the first (eager) warm-up update
+    if roofline and args.warmup > 0:  # FLOP by arithmetic of the first (eager) warm-up update
         from sdreamer import _native as nat
         census = FlopCensus(agent)
         nat.PROBES.append(census)
@@ -784,9 +830,11 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    post = _LastPosterior(buf) if args.dump_outputs and rank == 0 else None
+    mets = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        agent.update(buf)
+        mets = agent.update(buf)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -798,6 +846,8 @@ def main():
         dt = t.item()
     ms = dt / args.steps * 1000.0
     value = world * B * L * H * args.steps / dt
+    if post is not None and mets is not None:
+        dump_outputs(args.dump_outputs, mets, post)
 
     out = {
         "metric": METRIC,
@@ -835,7 +885,7 @@ def main():
         # per-launch time of an empty dispatch replayed the same way: the launch boundary inside the graph-timed figures
         from sdreamer import _native as nat
         out["graph_empty_dispatch_us"] = _graph_us(lambda i: nat.call("sd_trace_mark", 3, K.stream()), 40)
-    if not args.no_roofline:
+    if roofline:
         out["phases"] = phase_rooflines(agent, cfg, args.config, ms, table, census=census)
         sc = out["phases"]["observe_scan"]
         # the recurrent scan beside the dominant kernel: what bounds the observe phase (the dependent launch chain),
@@ -846,7 +896,7 @@ def main():
             "algorithmic_GBps": sc["algorithmic_GBps"], "algorithmic_frac_of_hbm": sc["algorithmic_frac_of_hbm"],
             "counter_GBps": sc.get("counter_GBps"), "counter_frac_of_hbm": sc.get("counter_frac_of_hbm"),
             "what": "RSSM.observe forward alone (phases.observe_scan)"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_legs:
         if args.config == "dmc/cnn":  # checker legs beside the CPU baseline
             out["parity"] = wm_loss_parity_full()
             out["parity_golden_small"] = wm_loss_parity()
