@@ -15,7 +15,6 @@ Differences by design (documented in DESIGN.md):
 """
 from __future__ import annotations
 
-import contextlib
 import copy
 import ctypes
 import math
@@ -36,16 +35,9 @@ from .networks import (Linear, MLPHead, MultiDecoder, MultiEncoder, Projector, R
 from .optim import LaProp, WarmupSchedule
 from .rssm import RSSM, STREAM_ACT, STREAM_IMG, STREAM_OBS_AUG, STREAM_POLICY, STREAM_POLICY_ACT
 
-# SDREAMER_S2_AFTER_SCAN=1 (schedule knob): the actor/critic phase starts after the scan backward (beside the encoder
-# backward) instead of right after the replay-value backward (beside the scan backward)
-S2_AFTER_SCAN = os.environ.get("SDREAMER_S2_AFTER_SCAN", "0") == "1"
-# graphed update, opt-in: the world-model heads' weight-gradient contractions leave phase M1 (which runs beside the
-# imagination and slows it) for phase M2d on main after the encoder backward. Measured: the imagination got 0.27 ms
-# faster but M2d (0.68 ms) outgrew the join slack it fills: 13.59 vs 13.34 ms per update, so off by default.
-DEFER_WM = os.environ.get("SDREAMER_DEFER_WM", "0") == "1"
-# graphed update: the first N queued encoder weight-gradient contractions (the last stages', queued first) run on main
-# after the first stage's backward (phase M2d) instead of on the side stream (S4), which ends the update
-S4_MAIN = int(os.environ.get("SDREAMER_S4_MAIN", "1"))  # measured: 0 -> 13.01, 1 -> 12.93, 2 -> 12.98 ms
+# graphed update: the first S4_MAIN queued encoder weight-gradient contractions (the last stages', queued first) run on
+# main after the first stage's backward (phase M2d) instead of on the side stream (S4), which ends the update
+S4_MAIN = 1  # measured: 0 -> 13.01, 1 -> 12.93, 2 -> 12.98 ms
 # SDREAMER_FUSED_SAMPLE=0: replayed updates sample through Buffer.sample() + copies instead of sample_into (A/B knob)
 FUSED_SAMPLE = os.environ.get("SDREAMER_FUSED_SAMPLE", "1") != "0"
 
@@ -56,40 +48,12 @@ FUSED_IMAG = os.environ.get("SDREAMER_FUSED_IMAG", "1") != "0"
 # actor layer 0, the imagined heads' batched value layer 0) instead of re-contracting the imagined feats;
 # SDREAMER_REUSE_H0=0 recomputes them (A/B knob)
 REUSE_H0 = os.environ.get("SDREAMER_REUSE_H0", "1") != "0"
-# SDREAMER_PRIO=1 (schedule knob): graph-replayed updates run the critical chain on high-priority streams and the filler
-# phases (M1, S2-S4) on normal-priority ones
-STREAM_PRIO = os.environ.get("SDREAMER_PRIO", "0") == "1"
 # SDREAMER_IMAG_NOISE=0: the imagined prior samples draw their Gumbel noise inside the sampler epilogue (per step)
 # instead of from one sd_imagine_noise launch ahead of the rollout (same values; A/B knob)
 IMAG_NOISE = os.environ.get("SDREAMER_IMAG_NOISE", "1") != "0"
-# SDREAMER_FILL_CUS=first:count (schedule knob): the filler phases (M1 beside the imagination, S2-S4 beside the backward)
-# replay on streams whose workgroups may run only on CUs [first, first + count) (sd_stream_create_cumask), so the
-# latency-bound chain beside them keeps the other CUs to itself; the chain's own streams stay unmasked
-FILL_CUS = os.environ.get("SDREAMER_FILL_CUS", "")
-# SDREAMER_AC_DEFER=1 (schedule knob): the actor / value weight-gradient contractions of phase S2 (the imagined
-# trajectories' large (H*N)-row GEMMs) are queued and run at the start of S3, beside the encoder backward, instead of
-# beside the scan backward (M2a, the latency-bound chain S2 slows)
-AC_DEFER = os.environ.get("SDREAMER_AC_DEFER", "0") == "1"
 # the imagined actor's and value head's first-layer weight gradients as ONE split-bf16 GEMM over their joint dy: the
 # 157 MB imagined-feature operand read once instead of twice (ops.PairFirstFn). 0 = one per head
 PAIR_FIRST = os.environ.get("SDREAMER_PAIR_FIRST", "1") != "0"
-# SDREAMER_SLOW_IN_S2=1: the imagined slow-critic head in the actor-critic phase S2 instead of with the other imagined
-# heads in S1 (which end the path to the lambda-returns and the replay-value loss). Measured slower (10.87 -> 10.91 ms
-# per update, profiles/r06f: the heads' batched first layer loses its fourth entry's reuse of the imagined features
-# and S2 beside the scan backward grows), so off
-SLOW_IN_S2 = os.environ.get("SDREAMER_SLOW_IN_S2", "0") == "1"
-# KB of dynamic LDS every GEMM launch of the filler phases (M1, S2, S3, S4) reserves without using it (sd_set_lds_pad):
-# fewer filler workgroups fit on a CU, leaving LDS for the latency-bound chain's workgroups beside them (0 = off)
-FILL_LDS = int(os.environ.get("SDREAMER_FILL_LDS", "0"))
-# S0: the imagination's noise and weight images (1), and also the scan backward's transposed and the encoder's flipped
-# weights (2), as a side-stream phase beside the encoder forward instead of at the head of S1 (imagination) and inside
-# M1. Measured neutral (profiles/r05v, r05w: the encoder forward slows by what S1 / M1 save; 3-round A/B 10.90 / 10.91 /
-# 10.96 ms for 0 / 1 / 2): off by default
-SIDE_PREP = int(os.environ.get("SDREAMER_SIDE_PREP", "0"))
-# SDREAMER_SIDE_PREP_AT=scan: S0 forks off after the encoder forward, beside the posterior scan (a latency-bound chain
-# of ~128-workgroup launches that leaves most CUs idle) instead of beside the compute-bound encoder: phase P gets a
-# split point there (parallel.collective) whose host step records an event and queues S0 on the side stream
-SIDE_PREP_AT = os.environ.get("SDREAMER_SIDE_PREP_AT", "enc")
 
 
 def _symexp_bins(n, device):  # symexp_twohot bins, distributions.py:242-251
@@ -108,23 +72,7 @@ def _tstats(t, prefix):  # tools.tensorstats (tools.py:275-281), resolved with t
     return K.tensorstats(t, prefix)
 
 
-
 IMAG_TRACE = None  # uint64 device tensor: per-launch / per-workgroup phase timestamps of the fused imagination
-_CUMASK = {}  # device -> the two CU-masked filler streams of SDREAMER_FILL_CUS (created once per process, never leaked
-# per agent: tests and benches build several agents)
-
-
-def _cumask_streams(device):
-    key = str(device)
-    if key not in _CUMASK:
-        first, count = (int(v) for v in FILL_CUS.split(":"))
-        mk = []
-        for _ in range(2):
-            h = ctypes.c_void_p()
-            nat.call("sd_stream_create_cumask", first, count, ctypes.addressof(h))
-            mk.append(torch.cuda.ExternalStream(h.value, device=device))
-        _CUMASK[key] = tuple(mk)
-    return _CUMASK[key]
 
 
 class Dreamer(nn.Module):
@@ -234,8 +182,7 @@ class Dreamer(nn.Module):
         a = self._optimizer.arena
         vparams = [p for n, p in self._named_params.items() if n.startswith("value.")]
         pos = {id(p): i for i, p in enumerate(a.params)}
-        idx = [pos[id(p)] for p in vparams]
-        self._v_lo, self._v_hi = a.offsets[idx[0]], a.offsets[idx[-1]] + a.sizes[idx[-1]]
+        self._v_lo, self._v_hi = self._arena_span([pos[id(p)] for p in vparams], "value.")
         self._slow_arena = a.data[self._v_lo:self._v_hi].clone()
         for p, sp in zip(vparams, self._slow_value.parameters()):
             j = pos[id(p)]
@@ -257,7 +204,6 @@ class Dreamer(nn.Module):
         # SDREAMER_MARKS=1: device timestamps at the phase boundaries of every update (kernels.Marks)
         self.marks = K.Marks(self.device) if os.environ.get("SDREAMER_MARKS", "0") != "0" else None
         self._side = torch.cuda.Stream(device=self.device)
-        self._prio_streams = None  # (main, side, fill, side fill) of STREAM_PRIO, created at the first replay
         # device 1.0: the seed gradient of the world-model total (no fill launch per update); made here, outside any
         # capture, so its value never depends on which update first asks for it
         self._one = torch.ones((), dtype=torch.float32, device=self.device)
@@ -293,15 +239,23 @@ class Dreamer(nn.Module):
     def _polyak(self):
         K.polyak(self._optimizer.arena.data[self._v_lo:self._v_hi], self._slow_arena, self.slow_target_fraction)
 
+    def _arena_span(self, idx, prefix):
+        """[lo, hi) of the arena slice that holds exactly the parameters `idx` (arena indices): they must be
+        physically back to back (FlatArena places tensors by its `order`, not by index)."""
+        a = self._optimizer.arena
+        by_off = sorted(idx, key=lambda i: a.offsets[i])
+        for prev, i in zip(by_off, by_off[1:]):
+            if a.offsets[i] != a.offsets[prev] + a.padded[prev]:
+                raise RuntimeError(f"{prefix} parameters are not contiguous in the arena")
+        return a.offsets[by_off[0]], a.offsets[by_off[-1]] + a.sizes[by_off[-1]]
+
     def _mirror(self, prefix, module):
         """A non-trainable copy of the contiguous arena slice holding `prefix`'s parameters; `module`'s parameters
         become views of it (DreamerPro's EMA encoder / obs projection)."""
         a = self._optimizer.arena
         pos = {id(p): i for i, p in enumerate(a.params)}
         idx = [pos[id(p)] for n, p in self._named_params.items() if n.startswith(prefix)]
-        if idx != list(range(idx[0], idx[0] + len(idx))):
-            raise RuntimeError(f"{prefix} parameters are not contiguous in the arena")
-        lo, hi = a.offsets[idx[0]], a.offsets[idx[-1]] + a.sizes[idx[-1]]
+        lo, hi = self._arena_span(idx, prefix)
         buf = a.data[lo:hi].clone()
         mps = list(module.parameters())
         if len(mps) != len(idx):
@@ -549,10 +503,9 @@ class Dreamer(nn.Module):
             self.marks(tag)
 
     def _main_tail(self, st):
-        """phase M2d (main, after the first encoder stage's backward): deferred weight gradients moved off the side
-        stream's tail (SDREAMER_DEFER_WM / SDREAMER_S4_MAIN)."""
-        ops.flush_wgrads(st.get("wm_wgrads", []))
-        ops.flush_wgrads(st.get("enc_wgrads_main", []))
+        """phase M2d (main, after the first encoder stage's backward): the first S4_MAIN queued encoder weight-gradient
+        contractions, moved off the side stream's tail (S4)."""
+        ops.flush_wgrads(st["enc_wgrads_main"])
         self._mark("main_tail")
 
     def _flush(self, wgrads, tag):
@@ -590,15 +543,26 @@ class Dreamer(nn.Module):
         self._mark("optimizer")
 
     def _update_graphed(self, data, initial, seed, ro):
-        """Replay of the update as eleven single-stream phases (captured once) joined by stream events:
+        """Replay of the update as twelve single-stream phases (captured once) joined by stream events. There is one
+        schedule: `main` is the caller's stream, `side` is self._side (or main with SDREAMER_SIDE_STREAM=0).
 
-            main: P (encoder, scan fwd) ─┬─ M1 (world-model heads, replay-value fwd) ─ wait(S1) ─ R (replay-value
-                                         │   loss + bwd) ─┬─ M2a (scan bwd) ─┬─ M2b (encoder stages 2.. bwd) ─┬─ M2c
-                                         │                │                  │                                │  (first
-                                         │                │                  │   stage) ─ wait(side) ─ [grad all-reduce] ─ M3
-            side:                        └─ S1 (imagination, heads, λ-returns) ─ wait(R) ─ S2 (value-head weight
-                                                grads, ReturnEMA, actor / critic) ─ wait(M2a) ─ S3 (scan weight grads)
-                                                ─ wait(M2b) ─ S4 (encoder stages 2.. weight grads)
+            main: P ─┬─ M1 ─ wait(S1) ─ R ─┬─ M2a ─┬─ M2b ─┬─ M2c ─ M2d ─ wait(side) ─ [grad all-reduce] ─ M3
+            side:    └─ S1 ────────────────┴─ S2 ──┴─ S3 ──┴─ S4
+
+        (S1 starts after P; S2 waits for R, S3 for M2a, S4 for M2b; M3 waits for S4.)
+
+            P    encoder forward, posterior scan forward (Polyak, preprocess)
+            S1   imagination, imagined heads (slow critic included), λ-returns
+            M1   world-model heads and their backward to the posterior leaves, replay-value forward
+            R    replay-value loss and its backward
+            M2a  scan backward (weight gradients queued for S3)
+            S2   the value head's replay-value weight gradients, ReturnEMA, actor / critic losses + backward, metrics
+            S3   the scan's weight gradients
+            M2b  encoder stages 2.. backward (weight gradients queued for S4 / M2d)
+            S4   encoder stages 2..'s weight gradients, all but the first S4_MAIN queued
+            M2c  first encoder stage's backward
+            M2d  the first S4_MAIN queued encoder weight gradients (_main_tail)
+            M3   optimizer step
 
         One graph per stream phase keeps every graph linear: the HIP runtime launches a linear graph as a batch
         (~0.5 ms of host time for the whole update) and the cross-stream edges become device-side event waits.
@@ -624,50 +588,34 @@ class Dreamer(nn.Module):
             mode = "global" if self.world == 1 else "thread_local"
             torch.cuda.synchronize()
 
-            def cap(fn, stream, fill=False):
-                if not (fill and FILL_LDS):
-                    return parallel.capture_phase(fn, stream, mode)
-                old = nat.fns["sd_set_lds_pad"](FILL_LDS * 1024)  # returns the previous pad
-                try:
-                    return parallel.capture_phase(fn, stream, mode)
-                finally:
-                    nat.fns["sd_set_lds_pad"](max(old, 0))
+            def cap(fn, stream):
+                return parallel.capture_phase(fn, stream, mode)
 
             # zero_grad folded into the optimizer step (M3 zeroes what it reads); the gradients are zeroed eagerly
             # before a replay whenever something else wrote them (_grads_clean)
             self._step_zeroes = True
             gP, st = cap(lambda: self._core_forward(self._g_in, self._g_init, self._seed_dev, ro), main_cap)
-            gS0, _ = cap(lambda: self._ph_side_prep(st), side_cap) if SIDE_PREP else (None, None)
             gS1, _ = cap(lambda: self._ph_side_returns(st), side_cap)
-            gM1, _ = cap(lambda: self._ph_wm(st, defer=DEFER_WM), main_cap, fill=True)
+            gM1, _ = cap(lambda: self._ph_wm(st), main_cap)
             gR, _ = cap(lambda: self._ph_repval(st), main_cap)
             gM2a, _ = cap(lambda: self._ph_scan_bwd(st, defer=True), main_cap)
-            if AC_DEFER:  # S2 captured before S3: its queued weight gradients are flushed at the start of S3
-                st["rr"]["ac_wgrads"] = []
-                gS2, (post, keys, mvec) = cap(lambda: self._side_ac_metrics(st), side_cap, fill=True)
-            gS3, _ = cap(lambda: self._flush(st["rr"].get("ac_wgrads", []) + st["scan_wgrads"], "side:scan_wgrads"),
-                         side_cap, fill=True)
+            gS3, _ = cap(lambda: self._flush(st["scan_wgrads"], "side:scan_wgrads"), side_cap)
             gM2b, _ = cap(lambda: self._ph_encoder_bwd_hi(st, defer=True), main_cap)
-            if S4_MAIN:
-                st["enc_wgrads_main"] = st["enc_wgrads"][:S4_MAIN]
-                del st["enc_wgrads"][:S4_MAIN]
-            gS4, _ = cap(lambda: self._flush(st["enc_wgrads"], "side:enc_wgrads"), side_cap, fill=True)
+            st["enc_wgrads_main"] = st["enc_wgrads"][:S4_MAIN]
+            del st["enc_wgrads"][:S4_MAIN]
+            gS4, _ = cap(lambda: self._flush(st["enc_wgrads"], "side:enc_wgrads"), side_cap)
             gM2c, _ = cap(lambda: self._ph_encoder_bwd_lo(st), main_cap)
-            gM2d = cap(lambda: self._main_tail(st), main_cap)[0] if (DEFER_WM or S4_MAIN) else None
-            if not AC_DEFER:
-                gS2, (post, keys, mvec) = cap(lambda: self._side_ac_metrics(st), side_cap, fill=True)
+            gM2d, _ = cap(lambda: self._main_tail(st), main_cap)
+            gS2, (post, keys, mvec) = cap(lambda: self._side_ac_metrics(st), side_cap)
             self._optimizer.zero_grads_after = True
             gM3, _ = cap(lambda: self._core_step(st), main_cap)
             self._optimizer.zero_grads_after = False  # eager steps (step()) keep the PyTorch semantics
             self._grads_clean = False
             torch.cuda.synchronize()
-            for g in (gS0, gP, gR, gM2a, gS3, gM2b, gS4, gM2c, gM2d, gM3):
-                if g is gP and SIDE_PREP and SIDE_PREP_AT == "scan":
-                    if g.n_collectives != 1:
-                        raise RuntimeError("P should hold exactly the S0 fork point")
-                elif g is not None and g.n_collectives:
+            for g in (gP, gR, gM2a, gS3, gM2b, gS4, gM2c, gM2d, gM3):
+                if g.n_collectives:
                     raise RuntimeError("unexpected exchange step in a single-graph phase")
-            self._graph = (gS0, gP, gS1, gM1, gR, gM2a, gS3, gM2b, gS4, gM2c, gM2d, gS2, gM3)
+            self._graph = (gP, gS1, gM1, gR, gM2a, gS3, gM2b, gS4, gM2c, gM2d, gS2, gM3)
             self._gst, self._g_post, self._g_keys, self._g_mvec = st, post, keys, mvec
         if data is not None:
             for k, v in data.items():
@@ -682,44 +630,19 @@ class Dreamer(nn.Module):
             self._ema_updates += 1
             self._proto_gate.copy_(torch.tensor([0.0 if self._protos_frozen() else 1.0]).pin_memory()
                                    .reshape(self._proto_gate.shape), non_blocking=True)
-        gS0, gP, gS1, gM1, gR, gM2a, gS3, gM2b, gS4, gM2c, gM2d, gS2, gM3 = self._graph
-        caller = torch.cuda.current_stream()
-        if STREAM_PRIO and self.use_side_stream:
-            # the critical chain (P, S1, R, M2a..M2d, M3) on high-priority streams, the phases that fill its idle CUs
-            # (M1 beside the imagination, S2-S4 beside the backward) on normal-priority ones: the dispatcher then
-            # serves a waiting critical-chain workgroup before a filler one
-            if self._prio_streams is None:
-                mk = lambda pr: torch.cuda.Stream(device=self.device, priority=pr)  # noqa: E731
-                self._prio_streams = (mk(-1), mk(-1), mk(0), mk(0))
-            main, side, fill, side_fill = self._prio_streams
-            main.wait_stream(caller)
-        elif FILL_CUS and self.use_side_stream:
-            if self._prio_streams is None:
-                self._prio_streams = _cumask_streams(self.device)
-            main, side = caller, self._side
-            fill, side_fill = self._prio_streams
-        else:
-            main = caller
-            side = self._side if self.use_side_stream else main
-            fill, side_fill = main, side
-        if gS0 is not None and SIDE_PREP_AT != "scan":  # S0 (weights and seed only) beside P: after the seed copy and
-            # the last optimizer step (SIDE_PREP_AT=scan: forked from P itself, _fork_side_prep)
-            if side is not main:
-                side.wait_stream(main)
-            with torch.cuda.stream(side):
-                gS0.replay()
+        gP, gS1, gM1, gR, gM2a, gS3, gM2b, gS4, gM2c, gM2d, gS2, gM3 = self._graph
+        main = torch.cuda.current_stream()
+        side = self._side if self.use_side_stream else main
         with torch.cuda.stream(main):
             if not self._grads_clean:
                 self._optimizer.zero_grad()
             gP.replay()
         if side is not main:
             side.wait_stream(main)
-        if fill is not main:
-            fill.wait_stream(main)
         k1 = gS1.first_collective()
         with torch.cuda.stream(side):
             gS1.replay(0, k1)
-        with torch.cuda.stream(fill):
+        with torch.cuda.stream(main):
             gM1.replay()
             ev_m1 = torch.cuda.Event()
             ev_m1.record()
@@ -730,8 +653,8 @@ class Dreamer(nn.Module):
             gS1.replay(k1)
             ev_s1 = torch.cuda.Event()
             ev_s1.record()
-        if dp and not DEFER_WM:  # heads bucket final after M1 (else after M2d); issued after S1's returns gather so
-            # RCCL's one communicator stream does not queue that gather (R waits on it) behind this all-reduce
+        if dp:  # heads bucket final after M1; issued after S1's returns gather so RCCL's one communicator stream
+            # does not queue that gather (R waits on it) behind this all-reduce
             self._allreduce_bucket("heads", ev_m1)
         main.wait_event(ev_m1)
         main.wait_event(ev_s1)
@@ -742,51 +665,38 @@ class Dreamer(nn.Module):
             gM2a.replay()
             ev_scan = torch.cuda.Event()
             ev_scan.record()
-            if S2_AFTER_SCAN:
-                ev_rep = ev_scan
             gM2b.replay()
             ev_enc = torch.cuda.Event()
             ev_enc.record()
             gM2c.replay()
-            if gM2d is not None:
-                gM2d.replay()
-        ev_side = [None, None]
-        if side_fill is not side:
-            side_fill.wait_stream(side)
-        with torch.cuda.stream(side_fill):
-            side_fill.wait_event(ev_rep)
+            gM2d.replay()
+        with torch.cuda.stream(side):
+            side.wait_event(ev_rep)  # S2: the actor-critic phase, beside the scan backward
             gS2.replay()
             if dp:
-                ev_side[0] = torch.cuda.Event()
-                ev_side[0].record()
-            side_fill.wait_event(ev_scan)  # S3: the scan's weight gradients, beside the encoder backward
+                ev_s2 = torch.cuda.Event()
+                ev_s2.record()
+            side.wait_event(ev_scan)  # S3: the scan's weight gradients, beside the encoder backward
             gS3.replay()
             if dp:
-                ev_side[1] = torch.cuda.Event()
-                ev_side[1].record()
-            side_fill.wait_event(ev_enc)  # S4: encoder stages 2..'s weight gradients, beside the first stage's backward
+                ev_s3 = torch.cuda.Event()
+                ev_s3.record()
+            side.wait_event(ev_enc)  # S4: encoder stages 2..'s weight gradients, beside the first stage's backward
             gS4.replay()
         if dp:  # bucketed sum all-reduce of the gradient arena, overlapping the backward phases still running
             ev_main, ev_s4 = torch.cuda.Event(), torch.cuda.Event()
             ev_main.record(main)
-            self._allreduce_bucket("ac", ev_side[1] if AC_DEFER else ev_side[0])
-            if DEFER_WM:  # the prior's img_net weight gradients are in M2d: the RSSM bucket also waits for main
-                self._allreduce_bucket("rssm", ev_side[1], ev_main)
-            else:
-                self._allreduce_bucket("rssm", ev_side[1])
-            ev_s4.record(side_fill)
-            if DEFER_WM:
-                self._allreduce_bucket("heads", ev_main)
+            self._allreduce_bucket("ac", ev_s2)
+            self._allreduce_bucket("rssm", ev_s3)
+            ev_s4.record(side)
             self._allreduce_bucket("rest", ev_main, ev_s4)
-        if side_fill is not main:
-            main.wait_stream(side_fill)
+        if side is not main:
+            main.wait_stream(side)
         if dp:
             main.wait_stream(self._comm)
         with torch.cuda.stream(main):
             gM3.replay()
         self._grads_clean = True
-        if main is not caller:
-            caller.wait_stream(main)
         self._slow_value_updates += 1
         self._optimizer.host_steps += 1
         self._updates += 1
@@ -853,8 +763,6 @@ class Dreamer(nn.Module):
         split = []  # the first encoder stage is backpropagated separately (_ph_encoder_bwd_lo)
         embed = self.encoder(data, split=split)
         mk("encoder_fwd")
-        if SIDE_PREP and SIDE_PREP_AT == "scan" and parallel._active is not None:  # (graph capture of P only)
-            parallel.collective(self._fork_side_prep)
         # the scan sees a leaf copy of embed: its backward stops there, so scan and encoder backward are separate
         # phases (_ph_scan_bwd / _ph_encoder_bwd)
         embed_l = embed.detach().requires_grad_(embed.requires_grad)
@@ -885,31 +793,6 @@ class Dreamer(nn.Module):
                     post_deter=post_deter, post_logit=post_logit, leaves=leaves, feat_l=feat_l, feat_r=feat_r,
                     ifeats=ifeats, fsink=fsink)
 
-    def _fork_side_prep(self):
-        """P's split point after the encoder forward (SIDE_PREP_AT=scan), run on the host between P's two graphs at
-        every replay: S0 on the side stream, after what main has queued so far (weights of the last step, the seed)."""
-        g = self._graph
-        if g is None or g[0] is None or not self.use_side_stream:
-            return
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self._side.wait_event(ev)
-        with torch.cuda.stream(self._side):
-            g[0].replay()
-
-    def _ph_side_prep(self, st):
-        """side, beside the encoder forward (S0): what depends on the weights and the seed only — the imagination's
-        noise and weight images (_imagine_prepare), the scan backward's transposed weights and the encoder's flipped
-        conv weights (read by the backward phases)."""
-        data = st["data"]
-        B, T = data["action"].shape[:2]
-        if self._fused_imag_ok():
-            st["imag_prep"] = self._imagine_prepare(B * T, self.imag_horizon + 1, st["seed"], st["ro"] * T,
-                                                    data["action"].device)
-        if SIDE_PREP >= 2:
-            st["scan_tr"] = self.rssm._bwd_tr = self.rssm.scan_bwd_weights()
-            st["enc_flip"] = K.set_flip_cache(self.encoder.dgrad_weights())
-
     def _ph_side_returns(self, st):
         """side: imagination (dreamer.py:578-597), imagined heads, lambda-returns + ReturnEMA (598-636)."""
         data = st["data"]
@@ -921,29 +804,24 @@ class Dreamer(nn.Module):
         # actor layer 0's fp32 output of every imagined step, kept for the policy loss's actor forward (REUSE_H0)
         ah0 = torch.empty(H1, N, self.actor.mlp.out_dim, device=start[1].device) \
             if REUSE_H0 and self._fused_imag_ok() and not self.actor.mlp._symlog_inputs else None
-        ifeat, iact = self._imagine_tm(start, H1, st["seed"], st["ro"] * T, actor_h0=ah0, feats=st.get("ifeats"),
-                                       prep=st.get("imag_prep"))
+        ifeat, iact = self._imagine_tm(start, H1, st["seed"], st["ro"] * T, actor_h0=ah0, feats=st.get("ifeats"))
         self._mark("side:imagine")
         rr = self._heads_returns(ifeat)
         rr["act_h0"] = ah0
         self._mark("side:heads_returns")
         st.update(ifeat=ifeat, iact=iact, rr=rr)
 
-    def _ph_wm(self, st, defer=False):
+    def _ph_wm(self, st):
         """main: world-model head losses and their backward down to the posterior leaves; the replay-value parts
-        that do not need the imagined returns. defer: the heads' weight-gradient contractions are queued in
-        st["wm_wgrads"] (graphed update: phase M2d)."""
-        st["wm_wgrads"] = []
+        that do not need the imagined returns."""
         # the scan backward's transposed weights and the encoder's flipped conv weights, while main has slack (it
         # waits for the imagined returns next): off the chain from the head losses to the encoder gradient
-        if "scan_tr" not in st:  # (made by _ph_side_prep when that phase ran)
-            st["scan_tr"] = self.rssm._bwd_tr = self.rssm.scan_bwd_weights()
-            st["enc_flip"] = K.set_flip_cache(self.encoder.dgrad_weights())
+        st["scan_tr"] = self.rssm._bwd_tr = self.rssm.scan_bwd_weights()
+        st["enc_flip"] = K.set_flip_cache(self.encoder.dgrad_weights())
         st["flags"] = self._episode_flags(st["data"])
-        with ops.defer_wgrads(st["wm_wgrads"] if defer else None):
-            st["wm_total"], st["wm_losses"], st["wm_metrics"] = self._wm_heads(st["data"], st["embed"], st["leaves"],
-                                                                               st["feat_l"], st["seed"], st["ro"],
-                                                                               st["initial"], st["flags"])
+        st["wm_total"], st["wm_losses"], st["wm_metrics"] = self._wm_heads(st["data"], st["embed"], st["leaves"],
+                                                                           st["feat_l"], st["seed"], st["ro"],
+                                                                           st["initial"], st["flags"])
         self._mark("wm_heads")
         st["rv"] = self._repval_pre(st["data"], st["feat_r"], st["flags"])
         self._mark("repval_fwd")
@@ -1028,7 +906,6 @@ class Dreamer(nn.Module):
         """side: the replay-value loss's deferred value-head weight gradients, ReturnEMA + advantage, policy / value
         losses on the imagined trajectories and their backward."""
         ops.flush_wgrads(st["rv_wgrads"])
-        self._slow_values(st["ifeat"], st["rr"])
         self._returns_norm(st["rr"])
         st["ac_losses"], st["ac_metrics"] = self._ac_losses(st["ifeat"], st["iact"], st["rr"])
         with torch.no_grad():  # replay-value statistics (dreamer.py:649-651), off the main stream's critical path
@@ -1235,15 +1112,14 @@ class Dreamer(nn.Module):
         # frozen heads on the imagined trajectories: split-bf16 contractions (no sampled index depends on them), the
         # four first layers as one batched launch
         firsts = []
-        # the slow critic feeds only the value loss's target and a metric (dreamer.py:606,616,666): with SLOW_IN_S2 it
-        # runs in the actor-critic phase (_slow_values), off the path from the imagination to the lambda-returns
-        heads = (self.reward, self.cont, self.value) + (() if SLOW_IN_S2 else (self._slow_value,))
-        outs = heads_nograd(heads, flat, True, firsts_out=firsts)
-        l_rew, l_cont, l_val = outs[:3]
+        # the slow critic feeds only the value loss's target and a metric (dreamer.py:606,616,666); it still runs here,
+        # as the fourth head: its first layer shares the batched launch's read of the imagined feats
+        heads = (self.reward, self.cont, self.value, self._slow_value)
+        l_rew, l_cont, l_val, l_slow = heads_nograd(heads, flat, True, firsts_out=firsts)
         i_rew = K.twohot_mode(l_rew, self.rbins).view(H1, N)
         i_contl = l_cont.reshape(H1, N)  # a column of the fused output layer's padded logits
         i_val = K.twohot_mode(l_val, self.vbins).view(H1, N)
-        i_slow = None if SLOW_IN_S2 else K.twohot_mode(outs[3], self.vbins).view(H1, N)
+        i_slow = K.twohot_mode(l_slow, self.vbins).view(H1, N)
         disc = 1 - 1 / self.horizon
         i_cont = torch.empty(N, H1, device=dev)
         weight = torch.empty(N, H1, device=dev)
@@ -1254,15 +1130,6 @@ class Dreamer(nn.Module):
         # (_frozen_value aliases value; the weights change only at the optimizer step)
         val_h0 = firsts[0][2] if (firsts and REUSE_H0) else None
         return dict(ret=ret, weight=weight, i_cont=i_cont, i_rew=i_rew, i_val=i_val, i_slow=i_slow, val_h0=val_h0)
-
-    @torch.no_grad()
-    def _slow_values(self, ifeat, rr):
-        """The slow critic's mode on the imagined trajectories (dreamer.py:593 _frozen_slow_value(imag_feat).mode()),
-        when _heads_returns left it out (SLOW_IN_S2)."""
-        if rr.get("i_slow") is None:
-            H1, N = ifeat.shape[:2]
-            (l_slow,) = heads_nograd((self._slow_value,), ifeat.reshape(H1 * N, -1), True)
-            rr["i_slow"] = K.twohot_mode(l_slow, self.vbins).view(H1, N)
 
     @torch.no_grad()
     def _returns_norm(self, rr):
@@ -1308,8 +1175,7 @@ class Dreamer(nn.Module):
             vl, logpi, ent, self.vbins, ret, i_slow[:H], weight, rr["i_val"], rr["ret_scale"], self.act_entropy,
             self._loss_scales["policy"], self._loss_scales["value"])
         rr["adv"] = adv
-        with ops.defer_wgrads(rr["ac_wgrads"]) if "ac_wgrads" in rr else contextlib.nullcontext():
-            torch.autograd.backward(total, self._unit(total.device))
+        torch.autograd.backward(total, self._unit(total.device))
         with torch.no_grad():
             # mean((ret - offset) / scale) as (mean(ret) - offset) / scale, resolved with the other metrics
             metrics["ret"] = K.Stat(ret, sub=rr["ret_offset"].reshape(1), div=rr["ret_scale"].reshape(1))
@@ -1341,9 +1207,8 @@ class Dreamer(nn.Module):
 
     def _imagine_prepare(self, N, H1, seed, row_offset, device):
         """The imagination's descriptor, workspace and everything in it that depends on the weights and the seed only:
-        the drawn-ahead noise (sd_imagine_noise) and the pre-split / transposed weight images (sd_imagine_prep). The
-        graphed update runs it as its own side-stream phase beside the encoder forward (S0), off the chain from the
-        posterior to the imagined returns; _imagine_fused(prep=...) then runs the steps."""
+        the drawn-ahead noise (sd_imagine_noise) and the pre-split / transposed weight images (sd_imagine_prep);
+        _imagine_fused then runs the steps."""
         r, a = self.rssm, self.actor
         P = r._p()
         d = nat.ImagineDesc()
@@ -1381,17 +1246,14 @@ class Dreamer(nn.Module):
             nat.call("sd_imagine_noise", ctypes.addressof(d), noise.data_ptr(), nact.data_ptr(), K.stream())
         nat.call("sd_imagine_prep", ctypes.addressof(d), K.stream())
         d.prepped = 1
-        return dict(desc=d, work=work, wo=wo, P=P, noise=noise, N=N, H1=H1)
+        return dict(desc=d, work=work, wo=wo, P=P, noise=noise)
 
-    def _imagine_fused(self, feats, actions, H1, seed, row_offset, chunks=None, keep=None, actor_h0=None, prep=None):
+    def _imagine_fused(self, feats, actions, H1, seed, row_offset, chunks=None, keep=None, actor_h0=None):
         """sd_imagine_run (csrc/img.hip): feats[0] holds the start state. chunks: step boundaries [t0, t1, ..., H1];
         the steps run as one launch sequence per chunk with an event recorded after each (returned), so consumers on
-        other streams can start on a chunk's feats while the next chunk is imagined. prep: _imagine_prepare's result
-        for this shape and seed (made here when None)."""
+        other streams can start on a chunk's feats while the next chunk is imagined."""
         N = feats.shape[1]
-        if prep is None:
-            prep = self._imagine_prepare(N, H1, seed, row_offset, feats.device)
-        assert prep["N"] == N and prep["H1"] == H1, (prep["N"], prep["H1"], N, H1)
+        prep = self._imagine_prepare(N, H1, seed, row_offset, feats.device)
         d = prep["desc"]
         d.feats, d.actions = feats.data_ptr(), actions.data_ptr()
         if IMAG_TRACE is not None:  # measurement aid (tools/imag_trace.py, a -DSD_SCAN_TRACE build of the library)
@@ -1414,7 +1276,7 @@ class Dreamer(nn.Module):
                 events.append(ev)
         return events
 
-    def _imagine_tm(self, start, H1, seed, row_offset=0, chunks=None, actor_h0=None, feats=None, prep=None):
+    def _imagine_tm(self, start, H1, seed, row_offset=0, chunks=None, actor_h0=None, feats=None):
         """Dreamer._imagine (dreamer.py:673-692), time-major: feats (H1, N, F), actions (H1, N, A).
         The reference's last img_step (whose output is discarded) is skipped. With `chunks` (step boundaries) returns
         (feats, actions, events) with one event per chunk (see _imagine_fused). feats (fused path): a buffer whose
@@ -1432,7 +1294,7 @@ class Dreamer(nn.Module):
             if not preset:
                 feats[0, :, :SK] = s
                 feats[0, :, SK:] = h
-            events = self._imagine_fused(feats, actions, H1, seed, row_offset, chunks, actor_h0=actor_h0, prep=prep)
+            events = self._imagine_fused(feats, actions, H1, seed, row_offset, chunks, actor_h0=actor_h0)
             return (feats, actions, events) if chunks else (feats, actions)
         s, h = s.contiguous(), h.contiguous()
         for t in range(H1):

@@ -252,7 +252,7 @@ def test_update_matches_reference(name):
     report["bound_ratio"] = {k: {"tensor": t, "ratio": r} for k, (t, r) in bounds.items()}
     report["bound_ratio_f64"] = {k: {"tensor": t, "ratio": r} for k, (t, r) in bounds64.items()}
     print(name, report)
-    if not os.environ.get("SDREAMER_GOLDEN_REPORT"):  # opt-in file report (tools/r05_*.sh set it)
+    if not os.environ.get("SDREAMER_GOLDEN_REPORT"):  # opt-in file report (set by one-off drivers, removed)
         return
     out = os.environ["SDREAMER_GOLDEN_REPORT"]
     os.makedirs(out, exist_ok=True)
@@ -423,33 +423,3 @@ def test_pair_first_matches_per_head():
             assert torch.equal(a, b), n
     assert checked == 4
 
-
-@pytest.mark.parametrize("at", ["enc", "scan"])
-def test_side_prep_graph_matches_eager(at, monkeypatch):
-    """The S0 side phase (SDREAMER_SIDE_PREP=2: the imagination's noise / weight images and the backward's weight
-    layouts beside the encoder forward, or forked from P after it, beside the scan: SDREAMER_SIDE_PREP_AT=scan) and the
-    filler LDS pad (SDREAMER_FILL_LDS) only move work between streams / change occupancy: graph replays equal the
-    eager updates exactly (cf. test_graph_replay_matches_eager)."""
-    import sdreamer.dreamer as D
-    monkeypatch.setattr(D, "SIDE_PREP", 2)
-    monkeypatch.setattr(D, "SIDE_PREP_AT", at)
-    monkeypatch.setattr(D, "FILL_LDS", 32)
-    runs = []
-    for graphs in (False, True):
-        ag, z, spec, obs = build_agent("walker_r2")
-        ag.use_graphs = graphs
-        out = []
-        for u in range(4):
-            (ps, pd), mets = ag.update_batch(batch(z, u % 2, obs, DEV), initial(z, u % 2, spec, DEV), 700 + u)
-            out.append((float(mets["loss/dyn"]), float(mets["loss/value"]), float(mets["opt/loss"]),
-                        pd.detach().clone()))
-        sd = ag.state_dict()
-        out.append(torch.cat([sd[k].reshape(-1) for k in spec.shapes]).clone())
-        runs.append(out)
-    e, g = runs
-    for u in range(4):
-        assert e[u][:3] == g[u][:3], (u, e[u][:3], g[u][:3])
-        assert torch.equal(e[u][3], g[u][3])
-    assert torch.equal(e[4], g[4])
-    from sdreamer import _native as nat
-    assert nat.fns["sd_lds_pad_failures"]() == 0  # every padded filler launch got its pad

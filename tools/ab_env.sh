@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of environment settings (schedule knobs, SDHIP_LIB variants) on bench.py: alternated R times, ms per
 # update printed per run. GPU box, repo root. Stops at the first failing run.
-# Usage: bash tools/ab_env.sh R "ENV_A" "ENV_B" [...]     e.g. bash tools/ab_env.sh 2 "" "SDREAMER_AC_DEFER=1"
+# Usage: bash tools/ab_env.sh R "ENV_A" "ENV_B" [...]     e.g. bash tools/ab_env.sh 2 "" "SDREAMER_PAIR_FIRST=0"
 R=$1; shift
 for i in $(seq "$R"); do
   for e in "$@"; do
