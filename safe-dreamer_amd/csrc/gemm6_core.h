@@ -53,108 +53,15 @@ SD_DEV void split3_store(__bf16* dst, f32x4 v) {
   *reinterpret_cast<bf16x4*>(dst + 2 * BK6) = __builtin_convertvector(l, bf16x4);
 }
 
-// split3_store with non-temporal stores (written for another XCD's next launch: streamed out of this XCD's L2)
-SD_DEV void split3_store_nt(__bf16* dst, f32x4 v) {
-  float h0, h1, h2, h3, m0, m1, m2, m3;
-  const u32x2 h{bf16_pair(v[0], v[1], h0, h1), bf16_pair(v[2], v[3], h2, h3)};
-  const float r0 = v[0] - h0, r1 = v[1] - h1, r2 = v[2] - h2, r3 = v[3] - h3;
-  const u32x2 m{bf16_pair(r0, r1, m0, m1), bf16_pair(r2, r3, m2, m3)};
-  const f32x4 l{r0 - m0, r1 - m1, r2 - m2, r3 - m3};
-  __builtin_nontemporal_store(h, reinterpret_cast<u32x2*>(dst));
-  __builtin_nontemporal_store(m, reinterpret_cast<u32x2*>(dst + BK6));
-  __builtin_nontemporal_store(__builtin_bit_cast(u32x2, __builtin_convertvector(l, bf16x4)),
-                              reinterpret_cast<u32x2*>(dst + 2 * BK6));
-}
-
 template <int N>
 SD_DEV __bf16* sd_smem6() {
   __shared__ __attribute__((aligned(16))) __bf16 s[N];
   return s;
 }
-template <int BM, int BN>
-constexpr int gemm6_smem_bf16() {
-  return 2 * (BM + BN) * LROW6;
-}
 
-// acc += A . B^T over [kbeg, kend) with PF k tiles in flight in registers and a double-buffered LDS image (one
-// barrier per tile), the structure of gemm16_mainloop_pf (late store behind a sched_barrier).
-template <int BM, int BN, int WM, int WN, int PF, class OpA, class OpB>
-SD_DEV void gemm6_mainloop_pf(OpA (&la)[PF], OpB (&lb)[PF], int kbeg, int kend, f32x4 (&acc)[WM / 16][WN / 16],
-                              bool accumulate = false) {
-  constexpr int WAVES_N = BN / WN;
-  constexpr int TM = WM / 16, TN = WN / 16;
-  static_assert((BM / WM) * (BN / WN) == 4, "4 waves");
-  constexpr int SA = BM * LROW6, STAGE = (BM + BN) * LROW6;
-  __bf16* smem = sd_smem6<2 * STAGE>();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave / WAVES_N, wc = wave % WAVES_N;
-  const int l16 = lane & 15, q = lane >> 4;
-  if (!accumulate) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  const int nk = (kend - kbeg + BK6 - 1) / BK6;
-  if (nk <= 0) return;
-  auto ktile = [&](int t) { return kbeg + (t < nk ? t : nk - 1) * BK6; };  // clamped: branch-free steady state
-#pragma unroll
-  for (int u = 0; u < PF; ++u) {
-    la[u].load(ktile(u), kend);
-    lb[u].load(ktile(u), kend);
-  }
-  la[0].store6(smem);
-  lb[0].store6(smem + SA);
-  __syncthreads();
-  la[0].load(ktile(PF), kend);
-  lb[0].load(ktile(PF), kend);
-  auto step = [&](int kt, int u) {
-    const __bf16* cur = smem + (kt & 1) * STAGE;
-    bf16x8 a[TM][3], b[TN][3];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const __bf16* p = cur + (wr * WM + 16 * i + l16) * LROW6 + 8 * q;
-#pragma unroll
-      for (int s = 0; s < 3; ++s) a[i][s] = *reinterpret_cast<const bf16x8*>(p + s * BK6);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const __bf16* p = cur + SA + (wc * WN + 16 * j + l16) * LROW6 + 8 * q;
-#pragma unroll
-      for (int s = 0; s < 3; ++s) b[j][s] = *reinterpret_cast<const bf16x8*>(p + s * BK6);
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        f32x4 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][2], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][1], b[j][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][0], b[j][2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][1], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][0], b[j][1], c, 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][0], b[j][0], c, 0, 0, 0);
-      }
-    const int nx = (u + 1) % PF;
-    __builtin_amdgcn_sched_barrier(0);
-    la[nx].store6(smem + ((kt & 1) ^ 1) * STAGE);
-    lb[nx].store6(smem + ((kt & 1) ^ 1) * STAGE + SA);
-    la[nx].load(ktile(kt + 1 + PF), kend);
-    lb[nx].load(ktile(kt + 1 + PF), kend);
-    __syncthreads();
-  };
-  int kt = 0;
-  for (; kt + PF <= nk; kt += PF) {
-#pragma unroll
-    for (int u = 0; u < PF; ++u) step(kt + u, u);
-  }
-#pragma unroll
-  for (int u = 0; u < PF; ++u)
-    if (kt + u < nk) step(kt + u, u);
-}
-
-// Single-stage form: half the LDS of gemm6_mainloop_pf (one staging buffer), two barriers per k tile (stage ->
-// barrier -> fragment reads -> barrier -> MFMAs, which run from registers while the next tile is staged). For
+// acc += A . B^T over [kbeg, kend) with PF k tiles in flight in registers. Single-stage form: one LDS staging buffer
+// (half of what the double-buffered gemm6_mainloop_fp below takes), two barriers per k tile (stage -> barrier ->
+// fragment reads -> barrier -> MFMAs, which run from registers while the next tile is staged). For
 // launches whose double-buffered LDS footprint would cap residency below the grid (k_gate: 2 -> 4 workgroups per CU,
 // its 1,024 workgroups in one round instead of two).
 template <int BM, int BN, int WM, int WN, int PF, class OpA, class OpB>

@@ -375,12 +375,7 @@ __global__ __launch_bounds__(NTHR) void k_hid(sd_rssm_scan d, Work w, int t) {
   const int grc = rv ? gr : rb + nr - 1;  // rows past the tile read the tile's last row (results discarded)
   const long tBU = (long)t * B * UH;
   f32x4 h[NG], x0[NU], x1[NU], x2v[NU], b0v[NU], b1v[NU], n0v[NU], n1v[NU];
-#ifndef SD_SCAN_PROBE_SLABS  // timing probe only (wrong results): k_hid reads / sums one x1p slab instead of ks_s
-#define SD_SCAN_PROBE_SLABS 0
-#endif
-  constexpr int KX1 = SD_SCAN_PROBE_SLABS ? 1 : KS1;
-  const int ks1 = SD_SCAN_PROBE_SLABS ? 1 : d.ks_s;
-  f32x4 x0p[X0F ? 1 : KSM][NU], x1p[KX1][NU];
+  f32x4 x0p[X0F ? 1 : KSM][NU], x1p[KS1][NU];
   ld_row(h, d.h_in + (long)t * B * D + (long)grc * D + (long)g * Dg, t32);
   if constexpr (X0F) {
     ld_row(x0, d.xcat + 3 * tBU + (long)grc * 3 * UH, t32);
@@ -389,7 +384,7 @@ __global__ __launch_bounds__(NTHR) void k_hid(sd_rssm_scan d, Work w, int t) {
     ld_row(b0v, d.b0, t32);
     ld_row(n0v, d.n0, t32);
   }
-  ld_slabs<NU, KX1>(x1p, w.x1s + (long)grc * UH, (long)B * UH, ks1, t32);
+  ld_slabs<NU, KS1>(x1p, w.x1s + (long)grc * UH, (long)B * UH, d.ks_s, t32);
   ld_row(b1v, d.b1, t32);
   ld_row(n1v, d.n1, t32);
   ld_row(x2v, d.x2 + in_row(d, t, grc) * UH, t32);
@@ -407,7 +402,7 @@ __global__ __launch_bounds__(NTHR) void k_hid(sd_rssm_scan d, Work w, int t) {
     for (int i = 0; i < NU; ++i) x0[i] += b0v[i];
     r0 = rms_silu_rows(x0, n0v, UH, d.eps, rv, y0);
   }
-  sum_slabs(x1, x1p, ks1);
+  sum_slabs(x1, x1p, d.ks_s);
 #pragma unroll
   for (int i = 0; i < NU; ++i) x1[i] += b1v[i];
   const float r1 = rms_silu_rows(x1, n1v, UH, d.eps, rv, y1);
@@ -608,9 +603,6 @@ __global__ __launch_bounds__(NTHR) void k_logit(sd_rssm_scan d, Work w, int t) {
 // nonzero per categorical (((k == idx) - ys) + ys is exactly 0 off the index), so its contraction with W1 is a gather
 // of CPG rows of W1^T: the NG = S / CPG slabs of a row sum (in k_hid's prologue, fixed order) to the dense product.
 // That removes the x1p k_slab launch from every step (4 dependent launches per step instead of 5).
-#ifndef LR_STAGE
-#define LR_STAGE 0  // measured slower in the update: 9.8 vs 8.9 us (128 KB of LDS: one workgroup per CU)
-#endif
 template <int KD, int CPG>
 __global__ __launch_bounds__(NTHR) void k_logit_rows(sd_rssm_scan d, Work w, int t) {
   constexpr int NC = CPG * KD, TPC = NTHR / NC, KPT = UH / TPC, NQ = KPT / 4;
@@ -622,18 +614,7 @@ __global__ __launch_bounds__(NTHR) void k_logit_rows(sd_rssm_scan d, Work w, int
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int B = d.B, SK = d.SK, S = SK / KD, g = blockIdx.x, b = blockIdx.y, n0 = g * NC;
   const long tBU = (long)t * B * UH;
-  // the gather's candidate rows — W1^T rows n0 .. n0 + NC (the group's categoricals x every index) — are loaded
-  // before the sample exists and staged in LDS (LR_STAGE: NC x U floats), so the gather after the sampler is an LDS
-  // read instead of a dependent global round trip
-  constexpr bool STAGE = LR_STAGE && NC * UH * 4 <= 131072;
-  constexpr int NW1 = STAGE ? NC * UH / 4 / NTHR : 1;
-  extern __shared__ __attribute__((aligned(16))) float w1s[];
-  f32x4 w1r[NW1];
   const bool more = t + 1 < d.T;
-  if (STAGE && more) {
-#pragma unroll
-    for (int i = 0; i < NW1; ++i) w1r[i] = ld4(w.w1t + (long)n0 * UH + 4 * (tid + NTHR * i));
-  }
   // independent of the contraction: the column's weight slice, bias, noise, reset mask
   const int col = tid / TPC, kp = tid % TPC;
   f32x4 wv[NQ];
@@ -759,17 +740,13 @@ __global__ __launch_bounds__(NTHR) void k_logit_rows(sd_rssm_scan d, Work w, int
     SD_TR_END(d.trace, d.trace_slot)
     return;
   }
-  if (STAGE) {
-#pragma unroll
-    for (int i = 0; i < NW1; ++i) *reinterpret_cast<f32x4*>(w1s + 4 * (tid + NTHR * i)) = w1r[i];
-  }
   __syncthreads();
   if (tid < UH) {  // slab g of x1p[t+1]: sum over the group's categoricals of v_s * W1^T[hot_s]
     float v = 0.f;
     if (!rnext) {
       float wr[CPG];
 #pragma unroll
-      for (int s = 0; s < CPG; ++s) wr[s] = STAGE ? w1s[hot[s] * UH + tid] : w.w1t[(long)(n0 + hot[s]) * UH + tid];
+      for (int s = 0; s < CPG; ++s) wr[s] = w.w1t[(long)(n0 + hot[s]) * UH + tid];
 #pragma unroll
       for (int s = 0; s < CPG; ++s) v = fmaf(hv[s], wr[s], v);
     }
@@ -1357,12 +1334,7 @@ int fwd_phase(const sd_rssm_scan& d, const Work& w, bool lrows, int which, int t
                                                                                         d.ks_d, rt));
   } else if (lrows) {
     const dim3 gr(LR_NG, B);
-#define SD_LR(KD_, CPG_)                                                                                 \
-  do {                                                                                                    \
-    constexpr size_t lds = LR_STAGE && (size_t)CPG_ * KD_ * UH * 4 <= 131072 ? (size_t)CPG_ * KD_ * UH * 4 : 0; \
-    if (!(raise_lds<k_logit_rows<KD_, CPG_>>(lds))) return SD_EARG;                                       \
-    k_logit_rows<KD_, CPG_><<<gr, NTHR, lds, st>>>(dd, w, t);                                             \
-  } while (0)
+#define SD_LR(KD_, CPG_) k_logit_rows<KD_, CPG_><<<gr, NTHR, 0, st>>>(dd, w, t)
     // CPG = S / LR_NG categoricals per workgroup (use_lrows: S % LR_NG == 0, so CPG >= 1 where it launches)
     if (d.Kd == 16) { if (SK == 512) SD_LR(16, lr_cpg(512, 16)); else SD_LR(16, lr_cpg(1024, 16)); }
     else if (d.Kd == 32) { if (SK == 512) SD_LR(32, lr_cpg(512, 32)); else SD_LR(32, lr_cpg(1024, 32)); }

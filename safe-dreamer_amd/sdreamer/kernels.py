@@ -65,15 +65,8 @@ def _skinny_split(M, N, K, batch):
     return max(1, min(ks, 64))
 
 
-# SDREAMER_F32_SPLIT2=1 (A/B knob): exact-f32 GEMMs of one round of 64 x 64 tiles (256..511) with K >= 1024 split K in
-# two (the world-model phase's 1024 x 1024 x 1024 Barlow contractions: 256 workgroups over 32 k tiles each)
-_F32_SPLIT2 = os.environ.get("SDREAMER_F32_SPLIT2", "0") == "1"
-
-
 def _auto_split(M, N, K, batch):
     tiles = -(-M // 64) * -(-N // 64) * batch
-    if _F32_SPLIT2 and 256 <= tiles < 512 and K >= 1024:
-        return 2
     if tiles >= 256 or K < 512:
         return 1
     ks = min(K // 256, max(1, 512 // tiles))
@@ -88,12 +81,7 @@ FAST_GEMM = os.environ.get("SDREAMER_FAST_GEMM", "1") != "0"
 # faster with more (1024: 157 vs 192 us), but in the update, beside the latency-bound scan backward, 512 measured
 # best (11.70 vs 11.80 ms at 1024, 11.76 at 2048 per update; gpurun_out r04v); again in round 5 against fewer
 # (10.70 vs 10.74 at 384, 10.86 at 256; profiles/r05wg)
-_G3_WG_TARGET = int(os.environ.get("SDREAMER_G3_WGS", "512"))
-# longest K chunk (rows) a split-bf16 workgroup takes when that needs more splits than the workgroup target — at most
-# twice as many (SDREAMER_G3_CHUNK, off). The atari-like config's 256 x 3072 x 30720 weight gradients go from 10
-# splits to 20 with 1536: 18.89 / 18.98 / 19.00 vs 18.89 / 18.89 / 18.85 ms per update, memory maze 74.30 vs 74.15
-# (gpurun_out r04c) — no gain.
-_G3_CHUNK = int(os.environ.get("SDREAMER_G3_CHUNK", "0"))
+_G3_WG_TARGET = 512
 
 
 def _fast_split(M, N, K, batch):
@@ -106,8 +94,6 @@ def _fast_split(M, N, K, batch):
         return 1
     if K >= 1024:
         wg = -(-_G3_WG_TARGET // tiles)
-        if _G3_CHUNK > 0:
-            wg = max(wg, min(-(-K // _G3_CHUNK), 2 * wg))
         cap = max(1, min(K // 512, wg, 32))
         if K % 32 == 0:
             kt = K // 32
@@ -120,21 +106,6 @@ def _fast_split(M, N, K, batch):
     if t64 >= 128 or K < 256:
         return 1
     return max(1, min(K // 128, -(-256 // t64), 16))
-
-
-_WGRAD_T128 = int(os.environ.get("SDREAMER_WGRAD_T128", "0"))
-
-
-def _wgrad_t128_split(M, N, K):
-    """split count for ~_WGRAD_T128 workgroups of 128 x 128 tiles, an even divisor of K's 32-deep tiles if one is near"""
-    tiles = -(-M // 128) * -(-N // 128)
-    want = max(1, min(32, round(_WGRAD_T128 / tiles), K // 512))
-    kt = K // 32 if K % 32 == 0 else 0
-    if kt:
-        for d in sorted(range(1, 33), key=lambda d: (abs(d - want), -d)):
-            if kt % d == 0 and abs(d - want) <= max(1, want // 4):
-                return d
-    return want
 
 
 def gemm(a, b, out, bias=None, alpha=1.0, beta=0.0, ksplit=None, tile=-1, fast=False, rowsum=None):
@@ -175,10 +146,6 @@ def gemm(a, b, out, bias=None, alpha=1.0, beta=0.0, ksplit=None, tile=-1, fast=F
     fast = fast and FAST_GEMM and M >= 64 and Nn >= 64 and K >= 64
     if rowsum is not None and not (fast and Bt == 1 and not ak and rowsum.is_contiguous()):
         return False
-    if ksplit is None and fast and _WGRAD_T128 and not ak and not bk and M <= 512 and K >= 4096 and tile < 0:
-        # weight-gradient shape (dW = dy^T x: long K, both operands rows-contiguous) on 128 x 128 tiles with about
-        # _WGRAD_T128 workgroups (SDREAMER_WGRAD_T128, A/B knob): fewer, longer split-K workgroups
-        ksplit, tile = _wgrad_t128_split(M, Nn, K), 0
     if ksplit is None:
         if fast:
             ksplit = _fast_split(M, Nn, K, Bt)
