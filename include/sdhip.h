@@ -318,6 +318,50 @@ int sd_pool_rms_bwd_compact(const float* pooled, const uint8_t* amax, const floa
                             const float* dy, float* dpool, float* dw, float* dw_partial, int Nb, int H, int W, int C,
                             int nchw_flat, int accumulate_dw, sd_stream stream);
 
+/* ---------------------------------------------------------------- text-conditioned (multimodal) encoder
+ * FiLM stage: y = silu(gamma[n / ipc][c] * rms(maxpool(conv))[c] + beta[n / ipc][c]); gamma / beta (Nb / ipc, C) f32,
+ * ipc = images per context row (Nb % ipc == 0, else SD_EARG). The forwards are the plain stage's kernels instantiated
+ * with the modulation in their epilogue: same shapes, same SD_ESHAPE rules, same pooled / amax / rstd. */
+int sd_conv2d_fwd_pool_film(const float* in, const float* w, const float* bias, const float* nw, const float* gamma,
+                            const float* beta, int ipc, float* pooled, uint8_t* amax, float* y, float* rstd, int Nb,
+                            int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad, float eps, int nchw_flat,
+                            sd_stream stream);
+int sd_conv2d_fwd_pool6_film(const float* in, const void* wsplit3, const float* bias, const float* nw,
+                             const float* gamma, const float* beta, int ipc, float* pooled, uint8_t* amax, float* y,
+                             float* rstd, int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad, float eps,
+                             int nchw_flat, sd_stream stream);
+int sd_pool_rms_fwd_film(const float* x, const float* w, const float* gamma, const float* beta, int ipc, float* pooled,
+                         uint8_t* amax, float* y, float* rstd, int Nb, int H, int W, int C, float eps, int nchw_flat,
+                         sd_stream stream);
+/* floats of film_partial below */
+int sd_film_grad_floats(int Nb, int ipc, int H, int W, int C);
+/* sd_pool_rms_bwd / _compact through the modulation: z is recomputed, dnorm = dz * gamma continues as there (dw: the
+ * norm weight's gradient, same partial layout); dgamma, dbeta (Nb / ipc, C) are overwritten with the sums over each
+ * context row's ipc * H/2 * W/2 pixels (per-workgroup partials added in a fixed order: deterministic). */
+int sd_pool_rms_bwd_film(const float* pooled, const uint8_t* amax, const float* w, const float* gamma,
+                         const float* beta, int ipc, const float* rstd, const float* dy, float* dx, float* dw,
+                         float* dw_partial, float* dgamma, float* dbeta, float* film_partial, int Nb, int H, int W,
+                         int C, int nchw_flat, int accumulate_dw, sd_stream stream);
+int sd_pool_rms_bwd_compact_film(const float* pooled, const uint8_t* amax, const float* w, const float* gamma,
+                                 const float* beta, int ipc, const float* rstd, const float* dy, float* dpool,
+                                 float* dw, float* dw_partial, float* dgamma, float* dbeta, float* film_partial, int Nb,
+                                 int H, int W, int C, int nchw_flat, int accumulate_dw, sd_stream stream);
+/* y[n] = silu(x[n] + u[n / T]) over (N, E) rows, u (N / T, E) or NULL (plain SiLU); backward: dx = dy silu'(.),
+ * du[b] = sum of its T rows of dx in row order (du may be NULL) */
+int sd_rowbias_silu_fwd(const float* x, const float* u, float* y, int N, int E, int T, sd_stream stream);
+int sd_rowbias_silu_bwd(const float* x, const float* u, const float* dy, float* dx, float* du, int N, int E, int T,
+                        sd_stream stream);
+/* text gate: g = sigmoid(a), out = v + g (tp[n / T] - v); v, a, out, g (N, E), tp (N / T, E).
+ * backward: dv = (1 - g) d, da = d (tp - v) g (1 - g), dtp[b] = sum of its T rows of g d in row order */
+int sd_text_gate_fwd(const float* v, const float* a, const float* tp, float* out, float* g, int N, int E, int T,
+                     sd_stream stream);
+int sd_text_gate_bwd(const float* v, const float* g, const float* tp, const float* d, float* dv, float* da,
+                     float* dtp, int N, int E, int T, sd_stream stream);
+/* attention pooling of ntexts texts' token features (ntexts, ntok, D): softmax over tokens of f . w + bias[0], then the
+ * weighted token sum -> out (ntexts, D); ntok <= 128 (else SD_ESHAPE) */
+int sd_text_pool(const float* feats, const float* w, const float* bias, float* out, int ntexts, int ntok, int D,
+                 sd_stream stream);
+
 /* ---------------------------------------------------------------- optimiser (flat parameter arena)
  * clip_grad_agc_ (agc.py:15-53) + LaProp.step (laprop.py:46-118) + LambdaLR warm-up (dreamer.py:214-225), fused.
  * chunk tables are device arrays built once by the caller; scalars = sd_opt_scalars_bytes() zeroed bytes of device

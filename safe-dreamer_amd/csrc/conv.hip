@@ -331,9 +331,23 @@ struct EpiPre {
   float bias[BN / 16];
   float nw[BN / 8];
 };
-template <int BN, int WM>
+// FiLM stage (multimodal encoder): y = silu(gamma[n / ipc][c] * norm + beta[n / ipc][c]) with gamma / beta (rows, C)
+// f32 and ipc images per context row. The stage kernels take their norm weight as a type NW: `const float*` is the
+// plain stage (signature and code as before), FilmNW adds the modulation. A tile can span images of two context rows
+// (8 x 8 stage: two images per 128 pixels), so gamma / beta are read per pooled pixel, not once per workgroup.
+struct FilmNW {
+  const float* nw;
+  const float* gamma;
+  const float* beta;
+  int ipc;
+};
+template <class NW> constexpr bool is_film = false;
+template <> constexpr bool is_film<FilmNW> = true;
+SD_DEV const float* nw_of(const float* nw) { return nw; }
+SD_DEV const float* nw_of(const FilmNW& f) { return f.nw; }
+template <int BN, int WM, class NW>
 SD_DEV void pool_epilogue(const f32x4 (&acc)[WM / 16][BN / 16], float* C, const GemmArgs& g, const Geom& G, int lw,
-                          int lhw, int bm0, const float* nw, float* pooled, uint8_t* amax, float* y, float* rstd,
+                          int lhw, int bm0, NW nw, float* pooled, uint8_t* amax, float* y, float* rstd,
                           float eps, int nchw_flat, const EpiPre<BN>* pre = nullptr) {
   constexpr int LDC = BN + 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l16 = lane & 15, q = lane >> 4;
@@ -383,10 +397,13 @@ SD_DEV void pool_epilogue(const f32x4 (&acc)[WM / 16][BN / 16], float* C, const 
   const float r = rsqrtf(ss / (float)BN + eps);
   if (valid && t8 == 0) rstd[gpp] = r;
   const long prem = gpp - (long)n * Ho * Wo;
+  long fo = 0;  // FiLM: this pixel's context row (row 0 for a pixel past the last image: nothing is stored for it)
+  if constexpr (is_film<NW>) fo = (long)(valid ? n / nw.ipc : 0) * BN;
 #pragma unroll
   for (int k = 0; k < NK; ++k) {
     const int c = t8 + 8 * k;
-    const float z = v[k] * r * (pre ? pre->nw[k] : nw[c]);
+    float z = v[k] * r * (pre ? pre->nw[k] : nw_of(nw)[c]);
+    if constexpr (is_film<NW>) z = nw.gamma[fo + c] * z + nw.beta[fo + c];
     const long o = nchw_flat ? (long)n * BN * Ho * Wo + (long)c * Ho * Wo + prem : gpp * BN + c;
     if (valid) y[o] = siluf_(z);
   }
@@ -398,8 +415,8 @@ SD_DEV void pool_epilogue(const f32x4 (&acc)[WM / 16][BN / 16], float* C, const 
 // A 128-pixel M tile holds whole 2x2 windows (128 % 2W == 0, image rows come in pairs), so the epilogue stages the
 // conv tile in the main loop's LDS area, pools it, normalises over the Co channels (8 threads per pooled pixel) and
 // writes only the pooled outputs (pooled pre-norm values, argmax, rstd for the backward; y NHWC or NCHW-flat).
-template <int BN, bool ES>
-__global__ __launch_bounds__(256) void conv_fwd16_pool(GemmArgs g, Geom G, int lw, int lhw, const float* nw,
+template <int BN, bool ES, class NW = const float*>
+__global__ __launch_bounds__(256) void conv_fwd16_pool(GemmArgs g, Geom G, int lw, int lhw, NW nw,
                                                        float* pooled, uint8_t* amax, float* y, float* rstd, float eps,
                                                        int nchw_flat) {
   __shared__ int tab[MAX_TAPQ];
@@ -410,7 +427,7 @@ __global__ __launch_bounds__(256) void conv_fwd16_pool(GemmArgs g, Geom G, int l
 #pragma unroll
   for (int j = 0; j < BN / 16; ++j) pre.bias[j] = g.bias ? g.bias[16 * j + (threadIdx.x & 15)] : 0.f;
 #pragma unroll
-  for (int k = 0; k < BN / 8; ++k) pre.nw[k] = nw[(threadIdx.x & 7) + 8 * k];
+  for (int k = 0; k < BN / 8; ++k) pre.nw[k] = nw_of(nw)[(threadIdx.x & 7) + 8 * k];
   f32x4 acc[WM / 16][BN / 16];
   if constexpr (ES) {
     Im2colRowsB<BM> la(G, tab, g.M, bm0, lw, lhw);
@@ -436,8 +453,8 @@ __global__ __launch_bounds__(256) void conv_fwd16_pool(GemmArgs g, Geom G, int l
 // (TM = 2) x all BN channels. A workgroup runs TPW vertically adjacent tiles (XCD-aware order: an XCD's workgroups
 // cover a contiguous tile range, so the KS - 1 halo rows adjacent tiles share are L2 hits), loading the next tile's
 // patch into registers under the current tile's MFMAs.
-template <int BN, int CI, int LW, int KS, int TPW>
-__global__ __launch_bounds__(256) void conv_fwd_direct_pool(GemmArgs g, Geom G, int lhw, const float* nw,
+template <int BN, int CI, int LW, int KS, int TPW, class NW = const float*>
+__global__ __launch_bounds__(256) void conv_fwd_direct_pool(GemmArgs g, Geom G, int lhw, NW nw,
                                                             float* pooled, uint8_t* amax, float* y, float* rstd,
                                                             float eps, int nchw_flat) {
   constexpr int BM = 128, WM = 32, TM = WM / 16, TN = BN / 16, W = 1 << LW, R = BM / W;
@@ -539,9 +556,9 @@ __global__ __launch_bounds__(256) void conv_fwd_direct_pool(GemmArgs g, Geom G, 
 // a chunk are 8 consecutive channels of one tap (CI % 8 == 0), so CI need not be a multiple of 32. Wave w owns tile
 // pixels 32w..32w+31 (two 16-pixel tiles) x all BN channels; the epilogue (pool + RMSNorm + SiLU) is
 // conv_fwd16_pool's, staged in the patch area.
-template <int BN, int CI, int LW, int KS>
+template <int BN, int CI, int LW, int KS, class NW = const float*>
 __global__ __launch_bounds__(256, 2) void conv_fwd6_direct_pool(GemmArgs g, Geom G, int lhw,
-                                                                 const __bf16* __restrict__ wsp, const float* nw,
+                                                                 const __bf16* __restrict__ wsp, NW nw,
                                                                  float* pooled, uint8_t* amax, float* y, float* rstd,
                                                                  float eps, int nchw_flat) {
   constexpr int W = 1 << LW, R = 128 / W, PH = R + KS - 1, PW = W + KS - 1, CP = CI + 8, PAD = KS / 2;
@@ -656,9 +673,10 @@ __global__ __launch_bounds__(256, 2) void conv_fwd6_direct_pool(GemmArgs g, Geom
 // (40 = 32 + a pad; 32 = packed, the 64-B rows of a fragment read are still 1 KB contiguous).
 // NTH: threads (the 48 -> 64 stage's whole image as four 64-pixel waves on 256 threads measured slower than eight
 // 32-pixel waves, 213.7 vs 180.5 us, profiles/r06m3: one wave per SIMD).
-template <int BN, int CI, int LW, int KS, bool CG, bool PIPE, int TPW, int MT = 2, int BROW = 40, int NTH = 512>
+template <int BN, int CI, int LW, int KS, bool CG, bool PIPE, int TPW, int MT = 2, int BROW = 40, int NTH = 512,
+          class NW = const float*>
 __global__ __launch_bounds__(NTH, 1) void conv_fwd6r_direct_pool(GemmArgs g, Geom G, int lhw,
-                                                                  const __bf16* __restrict__ wsp, const float* nw,
+                                                                  const __bf16* __restrict__ wsp, NW nw,
                                                                   float* pooled, uint8_t* amax, float* y, float* rstd,
                                                                   float eps, int nchw_flat) {
   constexpr int TP = 16 * MT * (NTH / 64);
@@ -856,9 +874,9 @@ __global__ __launch_bounds__(256) void split3_weight(const float* __restrict__ w
 // into registers under the current tile's MFMAs; the epilogue is conv_fwd16_pool's, in its own LDS area.
 // tpw (runtime) tiles per workgroup: the launcher sizes the grid to one round of resident workgroups (OCC per CU),
 // so no partial last round of long workgroups idles part of the chip.
-template <int BN, int LW, int KS, int OCC>
+template <int BN, int LW, int KS, int OCC, class NW = const float*>
 __global__ __launch_bounds__(256, OCC) void conv_fwd_direct_pool_c4(GemmArgs g, Geom G, int lhw, int TPW,
-                                                                    const float* nw, float* pooled, uint8_t* amax,
+                                                                    NW nw, float* pooled, uint8_t* amax,
                                                                     float* y, float* rstd, float eps, int nchw_flat) {
   constexpr int BM = 128, WM = 32, TM = WM / 16, TN = BN / 16, W = 1 << LW, R = BM / W;
   constexpr int PH = R + KS - 1, PW = W + KS - 1, PAD = KS / 2, NT = KS * KS;
@@ -884,7 +902,7 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_direct_pool_c4(GemmArgs g, 
 #pragma unroll
   for (int j = 0; j < TN; ++j) pre.bias[j] = g.bias ? g.bias[16 * j + l16] : 0.f;
 #pragma unroll
-  for (int k = 0; k < BN / 8; ++k) pre.nw[k] = nw[(threadIdx.x & 7) + 8 * k];
+  for (int k = 0; k < BN / 8; ++k) pre.nw[k] = nw_of(nw)[(threadIdx.x & 7) + 8 * k];
   const sd_rsrc rs = sd_make_rsrc(G.in, (long)G.Nb * G.Hs * G.Ws * 16);
   f32x4 v[NQT];
   auto load_patch = [&](int tile) {
@@ -1649,8 +1667,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(GemmArgs g, Geom G, int
 
 // ---------------------------------------------------------------- pooling / norm epilogues
 // y = silu(rms(maxpool2(x))) per output pixel (team of T lanes, VPT channels each); keeps pooled + argmax.
-template <int T, int VPT>
-__global__ void pool_rms_fwd(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ pooled,
+template <int T, int VPT, class NW = const float* __restrict__>
+__global__ void pool_rms_fwd(const float* __restrict__ x, NW w, float* __restrict__ pooled,
                              uint8_t* __restrict__ amax, float* __restrict__ y, float* __restrict__ rstd, int Nb, int H,
                              int W, int C, float eps, int nchw_flat) {
   const int Ho = H / 2, Wo = W / 2;
@@ -1685,11 +1703,14 @@ __global__ void pool_rms_fwd(const float* __restrict__ x, const float* __restric
   ss = group_sum<T>(ss);
   const float r = rsqrtf(ss / (float)C + eps);
   if (t == 0) rstd[pix] = r;
+  long fo = 0;
+  if constexpr (is_film<NW>) fo = (long)(n / w.ipc) * C;
 #pragma unroll
   for (int j = 0; j < VPT; ++j) {
     const int c = t + j * T;
     if (c < C) {
-      const float z = v[j] * r * w[c];
+      float z = v[j] * r * nw_of(w)[c];
+      if constexpr (is_film<NW>) z = w.gamma[fo + c] * z + w.beta[fo + c];
       const long o = nchw_flat ? (long)n * C * Ho * Wo + (long)c * Ho * Wo + rem : pix * C + c;
       y[o] = siluf_(z);
     }
@@ -1697,9 +1718,11 @@ __global__ void pool_rms_fwd(const float* __restrict__ x, const float* __restric
 }
 
 // COMPACT: dx is the pooled-resolution gradient (Nb, H/2, W/2, C) for sd_conv2d_wgrad_pool (no window scatter)
-template <int T, int VPT, bool COMPACT = false>
+// FiLM (NW = FilmNW): z = gamma * norm + beta is recomputed, the gradient continues as dnorm = dz * gamma (the norm
+// weight's partials are then sums of dz * gamma * xhat); dgamma / dbeta come from film_grad_partial below.
+template <int T, int VPT, bool COMPACT = false, class NW = const float* __restrict__>
 __global__ void pool_rms_bwd(const float* __restrict__ pooled, const uint8_t* __restrict__ amax,
-                             const float* __restrict__ w, const float* __restrict__ rstd, const float* __restrict__ dy,
+                             NW w, const float* __restrict__ rstd, const float* __restrict__ dy,
                              float* __restrict__ dx, float* __restrict__ dw_part, int Nb, int H, int W, int C,
                              int nchw_flat) {
   const int Ho = H / 2, Wo = W / 2;
@@ -1717,17 +1740,21 @@ __global__ void pool_rms_bwd(const float* __restrict__ pooled, const uint8_t* __
     const float r = rstd[pix];
     float xh[VPT], g[VPT];
     float dot = 0.f;
+    long fo = 0;
+    if constexpr (is_film<NW>) fo = (long)(n / w.ipc) * C;
 #pragma unroll
     for (int j = 0; j < VPT; ++j) {
       const int c = t + j * T;
       xh[j] = g[j] = 0.f;
       if (c < C) {
         const float xv = pooled[pix * C + c] * r;
-        const float wv = w[c];
-        const float z = xv * wv;
+        const float wv = nw_of(w)[c];
+        float z = xv * wv;
+        if constexpr (is_film<NW>) z = w.gamma[fo + c] * z + w.beta[fo + c];
         const float s = sigmoidf_(z);
         const long o = nchw_flat ? (long)n * C * Ho * Wo + (long)c * Ho * Wo + rem : pix * C + c;
-        const float dz = dy[o] * s * (1.f + z * (1.f - s));
+        float dz = dy[o] * s * (1.f + z * (1.f - s));
+        if constexpr (is_film<NW>) dz *= w.gamma[fo + c];
         xh[j] = xv;
         g[j] = dz * wv;
         dwacc[j] += dz * xv;
@@ -1764,6 +1791,70 @@ __global__ void pool_rms_bwd(const float* __restrict__ pooled, const uint8_t* __
     for (int tm = 0; tm < TPB; ++tm) s += wp[(tm * VPT + j) * T + tt];
     dw_part[(long)blockIdx.x * C + c] = s;
   }
+}
+
+// FiLM parameter gradients of a stage, first pass: workgroup (blk, b) walks context row b's ipc * Ho * Wo pooled pixels
+// (16 teams of 16 lanes, VPT channels per lane, as pool_rms_bwd), recomputes dz = dy * silu'(gamma * norm + beta) and
+// keeps S0 = sum dz, S1 = sum dz * xhat per channel; the 16 teams are added in team order and the block's sums go to
+// part[b][blk][2][C]. film_grad_final adds the blocks in block order: dbeta = S0, dgamma = nw * S1 (norm = xhat * nw).
+// No atomics: the result does not depend on the schedule.
+template <int T, int VPT>
+__global__ __launch_bounds__(256) void film_grad_partial(const float* __restrict__ pooled, const FilmNW w,
+                                                         const float* __restrict__ rstd,
+                                                         const float* __restrict__ dy, float* __restrict__ part,
+                                                         int Ho, int Wo, int C, int nchw_flat) {
+  const int t = threadIdx.x % T, team = threadIdx.x / T, b = blockIdx.y;
+  constexpr int TPB = 256 / T;
+  const int hw = Ho * Wo;
+  const long rowpix = (long)w.ipc * hw, pix0 = (long)b * rowpix;
+  float s0[VPT], s1[VPT];
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) s0[j] = s1[j] = 0.f;
+  for (long lp = (long)blockIdx.x * TPB + team; lp < rowpix; lp += (long)gridDim.x * TPB) {
+    const long pix = pix0 + lp;
+    const int n = (int)(pix / hw), rem = (int)(pix % hw);
+    const float r = rstd[pix];
+#pragma unroll
+    for (int j = 0; j < VPT; ++j) {
+      const int c = t + j * T;
+      if (c < C) {
+        const float xv = pooled[pix * C + c] * r;
+        const float z = w.gamma[(long)b * C + c] * (xv * w.nw[c]) + w.beta[(long)b * C + c];
+        const float s = sigmoidf_(z);
+        const long o = nchw_flat ? (long)n * C * hw + (long)c * hw + rem : pix * C + c;
+        const float dz = dy[o] * s * (1.f + z * (1.f - s));
+        s0[j] += dz;
+        s1[j] += dz * xv;
+      }
+    }
+  }
+  __shared__ float sp[2][TPB * T * VPT];
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) {
+    sp[0][(team * VPT + j) * T + t] = s0[j];
+    sp[1][(team * VPT + j) * T + t] = s1[j];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * C; i += 256) {
+    const int k = i / C, c = i % C, j = c / T, tt = c % T;
+    float s = 0.f;
+    for (int tm = 0; tm < TPB; ++tm) s += sp[k][(tm * VPT + j) * T + tt];
+    part[(((long)b * gridDim.x + blockIdx.x) * 2 + k) * C + c] = s;
+  }
+}
+
+__global__ void film_grad_final(const float* __restrict__ part, const float* __restrict__ nw,
+                                float* __restrict__ dgamma, float* __restrict__ dbeta, int rows, int nblk, int C) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * C) return;
+  const int b = i / C, c = i % C;
+  float s0 = 0.f, s1 = 0.f;
+  for (int k = 0; k < nblk; ++k) {
+    s0 += part[(((long)b * nblk + k) * 2 + 0) * C + c];
+    s1 += part[(((long)b * nblk + k) * 2 + 1) * C + c];
+  }
+  dbeta[i] = s0;
+  dgamma[i] = s1 * nw[c];
 }
 
 // Wf[ci][ky][kx][co] = W[co][kh-1-ky][kw-1-kx][ci]
@@ -1949,9 +2040,10 @@ extern "C" int sd_conv2d_fwd(const float* in, const float* w, const float* bias,
 
 // dw_db (Co, kh*kw*Ci + 1) = [dW | d bias] = sum over pixels of dout (Nb,Hg,Wg,Co) x im2col(in)
 // fused ConvEncoder stage forward; SD_ESHAPE when the shape is outside the fused kernel (caller: conv + pool)
-extern "C" int sd_conv2d_fwd_pool(const float* in, const float* w, const float* bias, const float* nw, float* pooled,
-                                  uint8_t* amax, float* y, float* rstd, int Nb, int Hs, int Ws, int Ci, int Co, int kh,
-                                  int kw, int pad, float eps, int nchw_flat, sd_stream stream_) {
+template <class NW>
+static int fwd_pool_impl(const float* in, const float* w, const float* bias, NW nw, float* pooled, uint8_t* amax,
+                         float* y, float* rstd, int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad,
+                         float eps, int nchw_flat, sd_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (Nb <= 0) return SD_OK;
   Geom G{in, Nb, Hs, Ws, Ci, Hs, Ws, kh, kw, pad, 0};
@@ -1972,8 +2064,8 @@ extern "C" int sd_conv2d_fwd_pool(const float* in, const float* w, const float* 
     const char* e = getenv("SDHIP_C32_TPW");
     const int tpw = e ? atoi(e) : 1;
 #define SD_C32(TPW)                                                                                                \
-  conv_fwd_direct_pool<48, 32, 5, 5, TPW><<<sd_cdiv(g.M / 128, TPW), 256, 0, s>>>(g, G, lhw, nw, pooled, amax, y, \
-                                                                                 rstd, eps, nchw_flat)
+  conv_fwd_direct_pool<48, 32, 5, 5, TPW, NW><<<sd_cdiv(g.M / 128, TPW), 256, 0, s>>>(g, G, lhw, nw, pooled, amax, \
+                                                                                     y, rstd, eps, nchw_flat)
     if (tpw == 4) SD_C32(4);
     else if (tpw == 1) SD_C32(1);
     else SD_C32(2);
@@ -1991,14 +2083,14 @@ extern "C" int sd_conv2d_fwd_pool(const float* in, const float* w, const float* 
     int tpw = e ? atoi(e) : 0;
     if (tpw <= 0) tpw = sd_cdiv(tiles, 256 * (occ > 0 ? occ : 4));
     const int nwg = sd_cdiv(tiles, tpw);
-    conv_fwd_direct_pool_c4<32, 6, 5, 4><<<nwg, 256, 0, s>>>(g, G, lhw, tpw, nw, pooled, amax, y, rstd, eps,
-                                                             nchw_flat);
+    conv_fwd_direct_pool_c4<32, 6, 5, 4, NW><<<nwg, 256, 0, s>>>(g, G, lhw, tpw, nw, pooled, amax, y, rstd, eps,
+                                                                 nchw_flat);
     SD_LAUNCH_CHECK();
     return SD_OK;
   }
-#define SD_FWDP(BN)                                                                                          \
-  (es ? conv_fwd16_pool<BN, true><<<grid, 256, 0, s>>>(g, G, lw, lhw, nw, pooled, amax, y, rstd, eps, nchw_flat) \
-      : conv_fwd16_pool<BN, false><<<grid, 256, 0, s>>>(g, G, lw, lhw, nw, pooled, amax, y, rstd, eps, nchw_flat))
+#define SD_FWDP(BN)                                                                                              \
+  (es ? conv_fwd16_pool<BN, true, NW><<<grid, 256, 0, s>>>(g, G, lw, lhw, nw, pooled, amax, y, rstd, eps, nchw_flat) \
+      : conv_fwd16_pool<BN, false, NW><<<grid, 256, 0, s>>>(g, G, lw, lhw, nw, pooled, amax, y, rstd, eps, nchw_flat))
   switch (Co) {
     case 16: SD_FWDP(16); break;
     case 32: SD_FWDP(32); break;
@@ -2009,6 +2101,23 @@ extern "C" int sd_conv2d_fwd_pool(const float* in, const float* w, const float* 
 #undef SD_FWDP
   SD_LAUNCH_CHECK();
   return SD_OK;
+}
+
+extern "C" int sd_conv2d_fwd_pool(const float* in, const float* w, const float* bias, const float* nw, float* pooled,
+                                  uint8_t* amax, float* y, float* rstd, int Nb, int Hs, int Ws, int Ci, int Co, int kh,
+                                  int kw, int pad, float eps, int nchw_flat, sd_stream stream_) {
+  return fwd_pool_impl(in, w, bias, nw, pooled, amax, y, rstd, Nb, Hs, Ws, Ci, Co, kh, kw, pad, eps, nchw_flat,
+                       stream_);
+}
+
+// the FiLM stage on the same kernels: gamma / beta (Nb / ipc, Co), ipc images per context row
+extern "C" int sd_conv2d_fwd_pool_film(const float* in, const float* w, const float* bias, const float* nw,
+                                       const float* gamma, const float* beta, int ipc, float* pooled, uint8_t* amax,
+                                       float* y, float* rstd, int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw,
+                                       int pad, float eps, int nchw_flat, sd_stream stream_) {
+  if (!gamma || !beta || ipc <= 0 || Nb % ipc) return SD_EARG;
+  return fwd_pool_impl(in, w, bias, FilmNW{nw, gamma, beta, ipc}, pooled, amax, y, rstd, Nb, Hs, Ws, Ci, Co, kh, kw,
+                       pad, eps, nchw_flat, stream_);
 }
 
 extern "C" int sd_conv2d_wgrad(const float* in, const float* dout, float* dw_db, float* workspace, long ws_floats,
@@ -2164,6 +2273,86 @@ extern "C" int sd_pool_rms_bwd_compact(const float* pooled, const uint8_t* amax,
   }
   SD_LAUNCH_CHECK();
   return sd_colsum_ws(dw_partial, dw, grid, C, C, accumulate_dw, dw_partial + (long)grid * C, stream_);
+}
+
+// FiLM stage: the two-launch forward, and the backward (dnorm through gamma, then sd_pool_rms_bwd's own chain; dgamma /
+// dbeta (rows, C) by film_grad_partial + film_grad_final, overwritten). film_partial >= sd_film_grad_floats floats.
+extern "C" int sd_pool_rms_fwd_film(const float* x, const float* w, const float* gamma, const float* beta, int ipc,
+                                    float* pooled, uint8_t* amax, float* y, float* rstd, int Nb, int H, int W, int C,
+                                    float eps, int nchw_flat, sd_stream stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  if (C > 128) return SD_ESHAPE;
+  if (!gamma || !beta || ipc <= 0 || Nb % ipc) return SD_EARG;
+  const long P = (long)Nb * (H / 2) * (W / 2);
+  if (P <= 0) return SD_OK;
+  const int grid = (int)((P * 16 + 255) / 256);
+  const FilmNW f{w, gamma, beta, ipc};
+  switch (vpt_for(C, 16)) {
+    case 1: pool_rms_fwd<16, 1, FilmNW><<<grid, 256, 0, s>>>(x, f, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat); break;
+    case 2: pool_rms_fwd<16, 2, FilmNW><<<grid, 256, 0, s>>>(x, f, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat); break;
+    case 4: pool_rms_fwd<16, 4, FilmNW><<<grid, 256, 0, s>>>(x, f, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat); break;
+    default: pool_rms_fwd<16, 8, FilmNW><<<grid, 256, 0, s>>>(x, f, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat); break;
+  }
+  SD_LAUNCH_CHECK();
+  return SD_OK;
+}
+
+static int film_grad_blocks(int ipc, int H, int W) {
+  const long b = ((long)ipc * (H / 2) * (W / 2) + 15) / 16;
+  return (int)(b < 64 ? (b > 0 ? b : 1) : 64);
+}
+
+extern "C" int sd_film_grad_floats(int Nb, int ipc, int H, int W, int C) {
+  if (ipc <= 0) return 0;
+  return (Nb / ipc) * film_grad_blocks(ipc, H, W) * 2 * C;
+}
+
+template <bool COMPACT>
+static int pool_rms_bwd_film_impl(const float* pooled, const uint8_t* amax, const float* w, const float* gamma,
+                                  const float* beta, int ipc, const float* rstd, const float* dy, float* dx, float* dw,
+                                  float* dw_partial, float* dgamma, float* dbeta, float* film_partial, int Nb, int H,
+                                  int W, int C, int nchw_flat, int accumulate_dw, sd_stream stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  if (C > 128) return SD_ESHAPE;
+  if (!gamma || !beta || !dgamma || !dbeta || !film_partial || ipc <= 0 || Nb % ipc) return SD_EARG;
+  if (Nb <= 0) return SD_OK;
+  const int grid = sd_pool_rms_bwd_blocks(Nb, H, W);
+  const FilmNW f{w, gamma, beta, ipc};
+  const int rows = Nb / ipc, nblk = film_grad_blocks(ipc, H, W);
+  const dim3 fgrid(nblk, rows);
+#define SD_FILM_BWD(V)                                                                                               \
+  pool_rms_bwd<16, V, COMPACT, FilmNW><<<grid, 256, 0, s>>>(pooled, amax, f, rstd, dy, dx, dw_partial, Nb, H, W, C,  \
+                                                            nchw_flat);                                              \
+  SD_LAUNCH_CHECK();                                                                                                 \
+  film_grad_partial<16, V><<<fgrid, 256, 0, s>>>(pooled, f, rstd, dy, film_partial, H / 2, W / 2, C, nchw_flat)
+  switch (vpt_for(C, 16)) {
+    case 1: SD_FILM_BWD(1); break;
+    case 2: SD_FILM_BWD(2); break;
+    case 4: SD_FILM_BWD(4); break;
+    default: SD_FILM_BWD(8); break;
+  }
+#undef SD_FILM_BWD
+  SD_LAUNCH_CHECK();
+  film_grad_final<<<sd_cdiv((long)rows * C, 256), 256, 0, s>>>(film_partial, w, dgamma, dbeta, rows, nblk, C);
+  SD_LAUNCH_CHECK();
+  return sd_colsum_ws(dw_partial, dw, grid, C, C, accumulate_dw, dw_partial + (long)grid * C, stream_);
+}
+
+extern "C" int sd_pool_rms_bwd_film(const float* pooled, const uint8_t* amax, const float* w, const float* gamma,
+                                    const float* beta, int ipc, const float* rstd, const float* dy, float* dx,
+                                    float* dw, float* dw_partial, float* dgamma, float* dbeta, float* film_partial,
+                                    int Nb, int H, int W, int C, int nchw_flat, int accumulate_dw, sd_stream stream_) {
+  return pool_rms_bwd_film_impl<false>(pooled, amax, w, gamma, beta, ipc, rstd, dy, dx, dw, dw_partial, dgamma, dbeta,
+                                       film_partial, Nb, H, W, C, nchw_flat, accumulate_dw, stream_);
+}
+
+extern "C" int sd_pool_rms_bwd_compact_film(const float* pooled, const uint8_t* amax, const float* w,
+                                            const float* gamma, const float* beta, int ipc, const float* rstd,
+                                            const float* dy, float* dpool, float* dw, float* dw_partial, float* dgamma,
+                                            float* dbeta, float* film_partial, int Nb, int H, int W, int C,
+                                            int nchw_flat, int accumulate_dw, sd_stream stream_) {
+  return pool_rms_bwd_film_impl<true>(pooled, amax, w, gamma, beta, ipc, rstd, dy, dpool, dw, dw_partial, dgamma,
+                                      dbeta, film_partial, Nb, H, W, C, nchw_flat, accumulate_dw, stream_);
 }
 
 // ---------------------------------------------------------------- split-bf16 backward entry points
@@ -2325,27 +2514,30 @@ bool conv6_pipe() {
   const char* e = getenv("SDHIP_CONV6_PIPE");
   return e ? atoi(e) != 0 : false;
 }
-template <int BN, int CI, int LW, int KS, bool CG, bool PIPE, int TPW, int MT = 2, int BROW = 40, int NTH = 512>
-int fwd6r_launch_t(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, const float* nw, float* pooled,
+template <int BN, int CI, int LW, int KS, bool CG, bool PIPE, int TPW, int MT = 2, int BROW = 40, int NTH = 512,
+          class NW>
+int fwd6r_launch_t(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, NW nw, float* pooled,
                    uint8_t* amax, float* y, float* rstd, float eps, int nchw_flat, size_t lds, hipStream_t s) {
   static bool raised = false;
   if (!raised) {
     if (hipFuncSetAttribute(
-            reinterpret_cast<const void*>(conv_fwd6r_direct_pool<BN, CI, LW, KS, CG, PIPE, TPW, MT, BROW, NTH>),
+            reinterpret_cast<const void*>(conv_fwd6r_direct_pool<BN, CI, LW, KS, CG, PIPE, TPW, MT, BROW, NTH, NW>),
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return SD_EARG;
     raised = true;
   }
   const int nwg = (sd_cdiv(g.M / (16 * MT * (NTH / 64)), TPW) + 7) / 8 * 8;  // a multiple of 8: XCD-contiguous
-  conv_fwd6r_direct_pool<BN, CI, LW, KS, CG, PIPE, TPW, MT, BROW, NTH><<<nwg, NTH, lds, s>>>(
+  conv_fwd6r_direct_pool<BN, CI, LW, KS, CG, PIPE, TPW, MT, BROW, NTH, NW><<<nwg, NTH, lds, s>>>(
       g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps, nchw_flat);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
 // SDHIP_CONV6_TPW: tiles per workgroup (1, 2, 4, 8, 16); default: enough for one workgroup per CU, at most 16.
+// FiLM stage: on the 32 -> 48 stage's 512-pixel tiles the knob is ignored (always one tile per workgroup: the
+// multi-tile variants there spill); every other shape honours it as the plain stage does.
 // (The fragment pipeline, SDHIP_CONV6_PIPE=1, runs one tile per workgroup: with the prefetched patch it spills.)
-template <int BN, int CI, int LW, int KS, bool CG>
-int fwd6r_launch(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, const float* nw, float* pooled,
+template <int BN, int CI, int LW, int KS, bool CG, class NW>
+int fwd6r_launch(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, NW nw, float* pooled,
                  uint8_t* amax, float* y, float* rstd, float eps, int nchw_flat, size_t lds, hipStream_t s) {
   if (conv6_pipe())
     return fwd6r_launch_t<BN, CI, LW, KS, CG, true, 1>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps, nchw_flat, lds,
@@ -2363,7 +2555,9 @@ int fwd6r_launch(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, c
 #define SD_F6R4(T) \
   fwd6r_launch_t<BN, CI, LW, KS, true, false, T, 4, 32>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps, nchw_flat, \
                                                         lds4, s)
-      return want <= 1 ? SD_F6R4(1) : want <= 4 ? SD_F6R4(4) : SD_F6R4(8);
+      // the multi-tile variants of this shape spill (a measurement knob): not instantiated for the FiLM stage
+      if constexpr (is_film<NW>) return SD_F6R4(1);
+      else return want <= 1 ? SD_F6R4(1) : want <= 4 ? SD_F6R4(4) : SD_F6R4(8);
 #undef SD_F6R4
     }
   }
@@ -2374,8 +2568,8 @@ int fwd6r_launch(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, c
   return want <= 1 ? SD_F6R(1) : want <= 2 ? SD_F6R(2) : want <= 4 ? SD_F6R(4) : want <= 8 ? SD_F6R(8) : SD_F6R(16);
 #undef SD_F6R
 }
-template <int BN, int CI, int LW>
-int fwd6_launch(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, const float* nw, float* pooled,
+template <int BN, int CI, int LW, class NW>
+int fwd6_launch(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, NW nw, float* pooled,
                 uint8_t* amax, float* y, float* rstd, float eps, int nchw_flat, hipStream_t s) {
   constexpr int W = 1 << LW, R = 128 / W, KS = 5;
   constexpr int R2 = 256 / W;
@@ -2388,21 +2582,22 @@ int fwd6_launch(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, co
   const size_t lds = (size_t)3 * (R + KS - 1) * (W + KS - 1) * (CI + 8) * 2;
   static bool raised = false;
   if (!raised && lds > 65536) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd6_direct_pool<BN, CI, LW, KS>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd6_direct_pool<BN, CI, LW, KS, NW>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return SD_EARG;
     raised = true;
   }
-  conv_fwd6_direct_pool<BN, CI, LW, KS><<<g.M / 128, 256, lds, s>>>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps,
+  conv_fwd6_direct_pool<BN, CI, LW, KS, NW><<<g.M / 128, 256, lds, s>>>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps,
                                                                    nchw_flat);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
 }  // namespace
 
-extern "C" int sd_conv2d_fwd_pool6(const float* in, const void* wsplit3, const float* bias, const float* nw,
-                                   float* pooled, uint8_t* amax, float* y, float* rstd, int Nb, int Hs, int Ws, int Ci,
-                                   int Co, int kh, int kw, int pad, float eps, int nchw_flat, sd_stream stream_) {
+template <class NW>
+static int fwd_pool6_impl(const float* in, const void* wsplit3, const float* bias, NW nw, float* pooled, uint8_t* amax,
+                          float* y, float* rstd, int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad,
+                          float eps, int nchw_flat, sd_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (Nb <= 0) return SD_OK;
   if (kh != 5 || kw != 5 || pad != 2 || Hs != Ws || Hs % 2 || !al16(in) || !al16(wsplit3)) return SD_ESHAPE;
@@ -2418,6 +2613,22 @@ extern "C" int sd_conv2d_fwd_pool6(const float* in, const void* wsplit3, const f
   if (Co == 64 && Ci == 48 && Ws == 16)
     return fwd6_launch<64, 48, 4>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps, nchw_flat, s);
   return SD_ESHAPE;
+}
+
+extern "C" int sd_conv2d_fwd_pool6(const float* in, const void* wsplit3, const float* bias, const float* nw,
+                                   float* pooled, uint8_t* amax, float* y, float* rstd, int Nb, int Hs, int Ws, int Ci,
+                                   int Co, int kh, int kw, int pad, float eps, int nchw_flat, sd_stream stream_) {
+  return fwd_pool6_impl(in, wsplit3, bias, nw, pooled, amax, y, rstd, Nb, Hs, Ws, Ci, Co, kh, kw, pad, eps, nchw_flat,
+                        stream_);
+}
+
+extern "C" int sd_conv2d_fwd_pool6_film(const float* in, const void* wsplit3, const float* bias, const float* nw,
+                                        const float* gamma, const float* beta, int ipc, float* pooled, uint8_t* amax,
+                                        float* y, float* rstd, int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw,
+                                        int pad, float eps, int nchw_flat, sd_stream stream_) {
+  if (!gamma || !beta || ipc <= 0 || Nb % ipc) return SD_EARG;
+  return fwd_pool6_impl(in, wsplit3, bias, FilmNW{nw, gamma, beta, ipc}, pooled, amax, y, rstd, Nb, Hs, Ws, Ci, Co,
+                        kh, kw, pad, eps, nchw_flat, stream_);
 }
 
 extern "C" int sd_conv_split_weight(const float* w, void* wsplit, int rows, int K, sd_stream stream_) {

@@ -40,7 +40,9 @@ def checkpoint_items(agent):
         "resume": {"updates": int(agent._updates), "slow_value_updates": int(agent._slow_value_updates),
                    "optimizer_host_steps": int(agent._optimizer.host_steps), "seed_base": int(agent._seed_base),
                    "ema_updates": int(getattr(agent, "_ema_updates", 0)),
-                   "moment_layout": "reference"},
+                   "moment_layout": "reference",
+                   # the multimodal encoder's text schedule (host state): a resumed run draws the same texts
+                   **({"text_schedule": agent.encoder.text_schedule_state()} if getattr(agent, "_mm", False) else {})},
     }
 
 
@@ -70,6 +72,8 @@ def load_checkpoint(agent, path, map_location=None):
         if hasattr(agent, "_ema_updates"):  # DreamerPro's EMA / prototype-freeze counter
             agent._ema_updates = int(res.get("ema_updates", 0))
         agent._seed_base = int(res["seed_base"])
+        if getattr(agent, "_mm", False) and "text_schedule" in res:
+            agent.encoder.load_text_schedule_state(res["text_schedule"])
     return ckpt
 
 

@@ -92,9 +92,30 @@ class Dreamer(nn.Module):
         self.rep_loss = str(config.rep_loss)
         self.rank, self.world = int(rank), int(world)
         shapes = {k: tuple(v.shape) for k, v in obs_space.spaces.items()}
-        if bool(config.use_multimodal_encoder):
-            raise NotImplementedError("multimodal CLIP encoder is out of scope (SURVEY.md §2: OUT OF SCOPE)")
-        self.encoder = MultiEncoder(config.encoder, shapes)
+        self._mm = bool(config.use_multimodal_encoder)
+        self._text_ctx = None
+        if self._mm:  # dreamer.py:37-61: FiLM + gate, or the ablations (film only: use_text_gate False; gate only)
+            if self.rep_loss == "dreamerpro":
+                raise NotImplementedError("rep_loss=dreamerpro with the multimodal encoder (its EMA encoder and second "
+                                          "posterior scan are not text-conditioned here)")
+            if self.world > 1:
+                raise NotImplementedError("the multimodal encoder on more than one GPU")
+            if set(k for k, v in shapes.items() if len(v) == 3) != {"image"}:
+                raise NotImplementedError("the multimodal encoder takes exactly one image observation, 'image'")
+            from .multimodal import GateOnlyEncoder, MultimodalEncoder
+            mc = config.multimodal_encoder
+            kind = str(config.get("ablation_encoder_type", "default") or "default")
+            if kind not in ("default", "gate_only"):
+                raise NotImplementedError(f"ablation_encoder_type={kind}")
+            cls = GateOnlyEncoder if kind == "gate_only" else MultimodalEncoder
+            self.encoder = cls(config.encoder.cnn, shapes["image"], text_context_dim=int(mc.text_context_dim),
+                               use_text_gate=bool(mc.use_text_gate), gate_init_bias=float(mc.gate_init_bias),
+                               seed_base=int(getattr(config, "seed", 0) or 0))
+            self.encoder.cnn_shapes = {"image": shapes["image"]}
+            if mc.get("text_features", None):
+                self.encoder.load_text_features(str(mc.text_features))
+        else:
+            self.encoder = MultiEncoder(config.encoder, shapes)
         self.embed_size = self.encoder.out_dim
         self.rssm = RSSM(config.rssm, self.embed_size, self.act_dim)
         self.reward = MLPHead(config.reward, self.rssm.feat_size)
@@ -129,7 +150,11 @@ class Dreamer(nn.Module):
             self._loss_scales.update({k: recon for k in self.decoder.all_keys})
             modules["decoder"] = self.decoder
         elif self.rep_loss in ("r2dreamer", "infonce"):
-            self.prj = Projector(self.rssm.feat_size, self.embed_size)
+            if self._mm:  # dreamer.py:118-121
+                from .multimodal import MLPProjector
+                self.prj = MLPProjector(self.rssm.feat_size, self.embed_size)
+            else:
+                self.prj = Projector(self.rssm.feat_size, self.embed_size)
             modules["projector"] = self.prj
             self.barlow_lambd = float(config.r2dreamer.lambd)
             aug = config.r2dreamer.aug
@@ -178,6 +203,17 @@ class Dreamer(nn.Module):
                                  agc=float(config.agc), pmin=float(config.pmin), warmup=int(config.warmup or 0),
                                  ref_layouts=self._ref_layouts, order=self._arena_order())
         self._scheduler = WarmupSchedule(self._optimizer)
+        if self._mm:
+            # the reference's optimizer also lists the text front end's four tensors (requires_grad there, but never
+            # given a gradient: LaProp skips them, so they hold a slot and no state). They keep their slots in the
+            # checkpoint's parameter order; here they are frozen parameters outside the arena.
+            full = [f"{name}.{pn}" for name, module in modules.items() if not isinstance(module, nn.Parameter)
+                    for pn, _ in module.named_parameters()
+                    if f"{name}.{pn}" in self._named_params or pn.startswith("text_context_encoder.")]
+            if len(full) != len(self._named_params) + 4 or any(isinstance(m, nn.Parameter) for m in modules.values()):
+                raise RuntimeError("unexpected parameter table for the multimodal encoder")
+            self._optimizer.ref_index = [full.index(n) for n in self._named_params]
+            self._optimizer.ref_count = len(full)
         # slow critic arena mirrors the value head's slice of the parameter arena (one Polyak kernel)
         a = self._optimizer.arena
         vparams = [p for n, p in self._named_params.items() if n.startswith("value.")]
@@ -224,7 +260,32 @@ class Dreamer(nn.Module):
         return super().to(*args, **kwargs)
 
     def set_task_name(self, task_name):  # dreamer.py:235-240 (no-op without the multimodal encoder)
-        pass
+        if self._mm:
+            self.encoder.set_task_name(task_name)
+
+    def set_text_features(self, texts, feats):
+        """The frozen text model's token features, one (N_tok, clip_dim) array per text (this build never runs CLIP)."""
+        if not self._mm:
+            raise ValueError("set_text_features needs model.use_multimodal_encoder=True")
+        self.encoder.set_text_features(texts, feats)
+
+    def _encode(self, data, split=None, both=True):
+        """-> (visual_embed, rssm_embed): the Barlow / InfoNCE target and the scan's input (dreamer.py:471-483); one
+        tensor twice without a text gate or with both=False (the augmented view: no gate). The text context was
+        refreshed eagerly by _refresh_text (a direct _cal_grad call refreshes it here)."""
+        if not self._mm:
+            e = self.encoder(data, split=split)
+            return e, e
+        if self._text_ctx is None:
+            self._refresh_text(data["action"].shape[0])
+        out = self.encoder(data, return_both=both, reuse_text_context=self._text_ctx, split=split)
+        return out if isinstance(out, tuple) else (out, out)
+
+    def _refresh_text(self, B):
+        """Eager, before the eager or replayed phases: this update's text context in the encoder's persistent buffer
+        (the graphs read it in place, so a text switch needs no re-capture)."""
+        if self._mm:
+            self._text_ctx = self.encoder.text_context(B, self.device)
 
     def train(self, mode=True):
         super().train(mode)
@@ -311,8 +372,13 @@ class Dreamer(nn.Module):
     def act(self, obs, state, eval=False, seed=None, step=0):
         """dreamer.py:330-357. obs: dict of (B, *) (image uint8), state: {stoch, deter, prev_action}."""
         p_obs = self.preprocess(dict(obs))
-        embed = self.encoder({k: v.unsqueeze(1) for k, v in p_obs.items() if k in self.encoder.cnn_shapes
-                              or k in self.encoder.mlp_shapes})[:, 0]
+        if self._mm:  # dreamer.py:337-341: the gated embed, the act-side text cache
+            ctx = self.encoder.act_context(p_obs["image"].shape[0], self.device, eval=eval)
+            out = self.encoder({"image": p_obs["image"]}, return_both=True, reuse_text_context=ctx)
+            embed = out[1] if isinstance(out, tuple) else out
+        else:
+            embed = self.encoder({k: v.unsqueeze(1) for k, v in p_obs.items() if k in self.encoder.cnn_shapes
+                                  or k in self.encoder.mlp_shapes})[:, 0]
         B = embed.shape[0]
         seed = self._seed_base + 7 if seed is None else seed
         stoch, deter, _ = self.rssm.obs_step(state["stoch"], state["deter"], state["prev_action"], embed,
@@ -338,7 +404,9 @@ class Dreamer(nn.Module):
             raise NotImplementedError("video_pred requires decoder and is only supported when rep_loss == 'dreamer'.")
         p = self.preprocess(dict(data))
         B = min(p["action"].shape[0], 6)
-        embed = self.encoder(p)
+        if self._mm:  # dreamer.py:378-381
+            self._refresh_text(p["action"].shape[0])
+        embed = self._encode(p)[1]
         ps, pd, _ = self.rssm.observe(embed[:B, :5], p["action"][:B, :5].contiguous(),
                                       tuple(v[:B].contiguous() for v in initial), p["is_first"][:B, :5].contiguous(),
                                       seed=seed)
@@ -362,6 +430,8 @@ class Dreamer(nn.Module):
         s_obs = {k: torch.zeros_like(v, device=dev) for k, v in obs_example.items()}
         s_state = self.get_initial_state(B)
         seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        if self._mm:  # the act-side context buffer exists before the capture; refreshed eagerly before each replay
+            self.encoder.act_context(B, dev, eval=eval)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -376,6 +446,8 @@ class Dreamer(nn.Module):
                 s_state[k].copy_(state[k])
             seed_dev.fill_(base + counter[0])
             counter[0] += 1
+            if self._mm:
+                self.encoder.act_context(B, dev, eval=eval)
             g.replay()
             return act, st
 
@@ -415,6 +487,7 @@ class Dreamer(nn.Module):
         graphs (set `use_graphs = False` to stay eager); multi-GPU runs split the graphs at the RCCL exchange steps
         (parallel.collective) and issue those eagerly between graph replays."""
         ro = self.rank * data["action"].shape[0] if row_offset is None else row_offset
+        self._refresh_text(data["action"].shape[0])
         if self.use_graphs and self.slow_target_update == 1 and \
                 (self.rep_loss != "dreamerpro" or self._pro["every"] == 1):
             if self._graph is not None or self._eager_updates >= 2:
@@ -439,6 +512,8 @@ class Dreamer(nn.Module):
         self._scheduler.step()
         mets["opt/lr"] = self._scheduler.get_lr()[0]
         mets["opt/grad_scale"] = 1.0
+        if self._mm:  # dreamer.py:438-440: the weight diagnostics, after the step
+            mets.update(self.encoder.weight_diagnostics())
         self._updates += 1
         return post, mets
 
@@ -577,6 +652,8 @@ class Dreamer(nn.Module):
         bucket's last writer phase is done — WM heads after M1, actor / value after S2, RSSM after S3, encoder at the
         end — so only the encoder bucket's all-reduce sits between the joins and M3 (which scales the arena by
         1/world before AGC + LaProp)."""
+        if data is None:  # update()'s replayed path samples straight into the graph inputs
+            self._refresh_text(self._g_in["action"].shape[0])
         if self._graph is None:
             self._g_in = {k: v.clone() for k, v in data.items()}
             self._g_ro = ro
@@ -704,6 +781,8 @@ class Dreamer(nn.Module):
         mets = {k: vec[i] for i, k in enumerate(self._g_keys)}
         mets["opt/lr"] = self._scheduler.get_lr()[0]
         mets["opt/grad_scale"] = 1.0
+        if self._mm:  # dreamer.py:438-440: the weight diagnostics, after the step
+            mets.update(self.encoder.weight_diagnostics())
         return self._g_post, mets
 
     def _cal_grad(self, data, initial, seed=0, row_offset=0):
@@ -761,11 +840,13 @@ class Dreamer(nn.Module):
         mk = self._mark
         mk("start")
         split = []  # the first encoder stage is backpropagated separately (_ph_encoder_bwd_lo)
-        embed = self.encoder(data, split=split)
+        # embed: the pure visual embed (Barlow / InfoNCE target); enc_out: what the scan reads (the text-gated embed
+        # with the multimodal encoder, else the same tensor) and where the encoder backward starts
+        embed, enc_out = self._encode(data, split=split)
         mk("encoder_fwd")
-        # the scan sees a leaf copy of embed: its backward stops there, so scan and encoder backward are separate
+        # the scan sees a leaf copy of enc_out: its backward stops there, so scan and encoder backward are separate
         # phases (_ph_scan_bwd / _ph_encoder_bwd)
-        embed_l = embed.detach().requires_grad_(embed.requires_grad)
+        embed_l = enc_out.detach().requires_grad_(enc_out.requires_grad)
         post_stoch, post_deter, post_logit = self.rssm.observe(embed_l, data["action"], initial, data["is_first"],
                                                                seed=seed, row_offset=ro)
         mk("scan_fwd")
@@ -788,7 +869,7 @@ class Dreamer(nn.Module):
         fsink = ops.DxSink(feat_l)
         ops.sink(feat_l, fsink)
         ops.sink(feat_r, fsink)
-        return dict(data=data, initial=initial, seed=seed, ro=ro, embed=embed, embed_l=embed_l,
+        return dict(data=data, initial=initial, seed=seed, ro=ro, embed=embed, enc_out=enc_out, embed_l=embed_l,
                     enc_split=split[0] if split else None, post_stoch=post_stoch,
                     post_deter=post_deter, post_logit=post_logit, leaves=leaves, feat_l=feat_l, feat_r=feat_r,
                     ifeats=ifeats, fsink=fsink)
@@ -890,9 +971,9 @@ class Dreamer(nn.Module):
         if g is not None:
             if defer:
                 with ops.defer_wgrads(st["enc_wgrads"]):
-                    st["embed"].backward(g)
+                    st["enc_out"].backward(g)
             else:
-                st["embed"].backward(g)
+                st["enc_out"].backward(g)
         K.clear_flip_cache()
 
     def _ph_encoder_bwd_lo(self, st):
@@ -921,6 +1002,8 @@ class Dreamer(nn.Module):
         losses.update(st["ac_losses"])
         metrics.update(st["rv_metrics"])
         metrics.update(st["ac_metrics"])
+        if self._mm:  # dreamer.py:438-440
+            metrics.update(self.encoder.gate_metrics())
         total = K.Stat(st["wm_total"].detach())
         for k, v in losses.items():
             if k in ("repval", "policy", "value"):
@@ -928,7 +1011,8 @@ class Dreamer(nn.Module):
         metrics.update({f"loss/{k}": v.detach() for k, v in losses.items()})
         metrics["opt/loss"] = total
         rr = st["rr"]
-        self._last = dict(embed=st["embed"], post_logit=st["post_logit"], prior_logit=self._prior_logit,
+        self._last = dict(embed=st["embed"], rssm_embed=st["enc_out"], post_logit=st["post_logit"],
+                          prior_logit=self._prior_logit,
                           imag_feat_tm=st["ifeat"], imag_action_tm=st["iact"], ret=rr["ret"], rret=st["rret"])
         return (st["post_stoch"], st["post_deter"]), metrics
 
@@ -966,7 +1050,7 @@ class Dreamer(nn.Module):
                     pad, same, bil = self.r2_aug
                     aug = {k: v for k, v in data.items() if k != "__enc_image"}  # the encoder re-forms its input
                     aug["image"] = K.random_translate(data["image"], pad, seed, ro, same, bil)
-                    x2 = self.encoder(aug).reshape(B * T, -1)
+                    x2 = self._encode(aug, both=False)[0].reshape(B * T, -1)  # the same text context (dreamer.py:502-538)
             else:
                 x2 = embed.reshape(B * T, -1).detach()
             losses["barlow"] = parallel.barlow(x1, x2, self.barlow_lambd, self.world)
@@ -1348,7 +1432,9 @@ class Dreamer(nn.Module):
         return sd
 
     def load_state_dict(self, state_dict, strict=True):
-        sd = OrderedDict((k, v) for k, v in state_dict.items() if not k.startswith("_frozen_"))
+        # the frozen CLIP weights a reference multimodal checkpoint carries are neither stored nor used here
+        sd = OrderedDict((k, v) for k, v in state_dict.items()
+                         if not k.startswith("_frozen_") and "text_context_encoder._text_model." not in k)
         out = super().load_state_dict(sd, strict=strict)
         self._optimizer.arena.rebind()
         a = self._optimizer.arena

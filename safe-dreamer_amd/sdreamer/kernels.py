@@ -304,19 +304,21 @@ def linear(x, w, b=None, out=None, beta=0.0, fast=False):
 
 
 # ------------------------------------------------------------------------------------------------- row norms
-def rmsnorm_fwd(x, w, act=1, y=None, rstd=None):
-    """y may be a column slice of a wider row-major tensor (unit column stride)."""
+def rmsnorm_fwd(x, w, act=1, y=None, rstd=None, eps=None):
+    """y may be a column slice of a wider row-major tensor (unit column stride). eps: default EPS (MLPProjector's
+    nn.RMSNorm(eps=None) passes float32 machine epsilon)."""
+    eps = EPS if eps is None else float(eps)
     x = _c(x)
     N = x.shape[-1]
     M = x.numel() // N
     y = torch.empty_like(x) if y is None else y
     rstd = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device) if rstd is None else rstd
     if y.is_contiguous():
-        nat.call("sd_rmsnorm_fwd", p(x), p(w), p(y), p(rstd), M, N, EPS, int(act), stream())
+        nat.call("sd_rmsnorm_fwd", p(x), p(w), p(y), p(rstd), M, N, eps, int(act), stream())
     else:
         if y.dim() != 2 or y.stride(1) != 1:
             raise ValueError("strided rmsnorm output must be a 2-D row-major slice")
-        nat.call("sd_rmsnorm_fwd_ld", p(x), p(w), p(y), y.stride(0), p(rstd), M, N, EPS, int(act), stream())
+        nat.call("sd_rmsnorm_fwd_ld", p(x), p(w), p(y), y.stride(0), p(rstd), M, N, eps, int(act), stream())
     return y, rstd
 
 
@@ -744,12 +746,28 @@ def sumpool2(du):
     return din
 
 
-def pool_rms_fwd(x, w, nchw_flat=False):
+def _film_args(film, Nb, C):
+    """(gamma, beta) (rows, C) contiguous f32, one row per Nb / rows consecutive images -> (gamma, beta, ipc)"""
+    gamma, beta = film
+    rows = gamma.shape[0]
+    if gamma.shape != (rows, C) or beta.shape != (rows, C) or rows <= 0 or Nb % rows:
+        raise ValueError(f"FiLM gamma / beta must be (rows, {C}) with rows dividing {Nb} images, got "
+                         f"{tuple(gamma.shape)} / {tuple(beta.shape)}")
+    return _c(gamma), _c(beta), Nb // rows
+
+
+def pool_rms_fwd(x, w, nchw_flat=False, film=None):
+    """film = (gamma, beta): the FiLM stage, z = gamma[n // ipc] * norm + beta[n // ipc] before the SiLU"""
     Nb, H, W, C = x.shape
     pooled = torch.empty(Nb, H // 2, W // 2, C, dtype=torch.float32, device=x.device)
     amax = torch.empty(Nb, H // 2, W // 2, C, dtype=torch.uint8, device=x.device)
     y = torch.empty_like(pooled)
     rstd = torch.empty(Nb, H // 2, W // 2, dtype=torch.float32, device=x.device)
+    if film is not None:
+        gamma, beta, ipc = _film_args(film, Nb, C)
+        nat.call("sd_pool_rms_fwd_film", p(_c(x)), p(w), p(gamma), p(beta), ipc, p(pooled), p(amax), p(y), p(rstd),
+                 Nb, H, W, C, EPS, int(nchw_flat), stream())
+        return y, pooled, amax, rstd
     nat.call("sd_pool_rms_fwd", p(_c(x)), p(w), p(pooled), p(amax), p(y), p(rstd), Nb, H, W, C, EPS, int(nchw_flat),
              stream())
     return y, pooled, amax, rstd
@@ -760,48 +778,124 @@ def ops_fused_pool():
     return ops.FUSED_POOL
 
 
-def conv2d_fwd_pool(x, w, b, nw, nchw_flat=False):
+def conv2d_fwd_pool(x, w, b, nw, nchw_flat=False, film=None):
     """Fused ConvEncoder stage forward (sd_conv2d_fwd_pool): x (Nb, H, W, Ci) NHWC, w (Co, kh, kw, Ci) ->
     (y, pooled, amax, rstd) as pool_rms_fwd(conv2d_fwd(x, w, b), nw) returns them, or None when the shape is outside
-    the fused kernel."""
+    the fused kernel. film = (gamma, beta): the same kernels with the FiLM modulation in their epilogue."""
     Nb, H, W, Ci = x.shape
     Co, kh, kw, _ = w.shape
     pooled = torch.empty(Nb, H // 2, W // 2, Co, dtype=torch.float32, device=x.device)
     amax = torch.empty(Nb, H // 2, W // 2, Co, dtype=torch.uint8, device=x.device)
     y = torch.empty_like(pooled)
     rstd = torch.empty(Nb, H // 2, W // 2, dtype=torch.float32, device=x.device)
+    sfx, fa = "", ()
+    if film is not None:
+        gamma, beta, ipc = _film_args(film, Nb, Co)
+        sfx, fa = "_film", (p(gamma), p(beta), ipc)
     if CONV6 and (CONV6 == "1" or (Ci, Co) == (32, 48)):  # fp32-accurate three-way split-bf16 direct kernel
         K = kh * kw * Ci
         ws = torch.empty(3 * Co * (-(-K // 32) * 32), dtype=torch.int16, device=x.device)
         nat.call("sd_conv_split3_weight", p(_c(w)), p(ws), Co, K, stream())
-        if nat.call_shaped("sd_conv2d_fwd_pool6", p(_c(x)), p(ws), p(b), p(nw), p(pooled), p(amax), p(y), p(rstd),
-                           Nb, H, W, Ci, Co, kh, kw, (kh - 1) // 2, EPS, int(nchw_flat), stream()):
+        if nat.call_shaped("sd_conv2d_fwd_pool6" + sfx, p(_c(x)), p(ws), p(b), p(nw), *fa, p(pooled), p(amax), p(y),
+                           p(rstd), Nb, H, W, Ci, Co, kh, kw, (kh - 1) // 2, EPS, int(nchw_flat), stream()):
             return y, pooled, amax, rstd
-    ok = nat.call_shaped("sd_conv2d_fwd_pool", p(_c(x)), p(_c(w)), p(b), p(nw), p(pooled), p(amax), p(y), p(rstd),
-                         Nb, H, W, Ci, Co, kh, kw, (kh - 1) // 2, EPS, int(nchw_flat), stream())
+    ok = nat.call_shaped("sd_conv2d_fwd_pool" + sfx, p(_c(x)), p(_c(w)), p(b), p(nw), *fa, p(pooled), p(amax), p(y),
+                         p(rstd), Nb, H, W, Ci, Co, kh, kw, (kh - 1) // 2, EPS, int(nchw_flat), stream())
     return (y, pooled, amax, rstd) if ok else None
 
 
-def pool_rms_bwd_compact(pooled, amax, w, rstd, dy, dw, nchw_flat=False):
-    """pool_rms_bwd writing the pooled-resolution gradient (Nb, H/2, W/2, C) instead of the scattered conv gradient."""
+def _film_bwd_args(film, Nb, H, W, C, device):
+    gamma, beta, ipc = _film_args(film, Nb, C)
+    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+    fpart = torch.empty(nat.fns["sd_film_grad_floats"](Nb, ipc, H, W, C), dtype=torch.float32, device=device)
+    return gamma, beta, ipc, dgamma, dbeta, fpart
+
+
+def pool_rms_bwd_compact(pooled, amax, w, rstd, dy, dw, nchw_flat=False, film=None):
+    """pool_rms_bwd writing the pooled-resolution gradient (Nb, H/2, W/2, C) instead of the scattered conv gradient.
+    film = (gamma, beta): returns (dpool, dgamma, dbeta)."""
     Nb, Ho, Wo, C = pooled.shape
     H, W = 2 * Ho, 2 * Wo
     dp = torch.empty_like(pooled)
     nb = nat.fns["sd_pool_rms_bwd_blocks"](Nb, H, W)
     part = torch.empty((nb + nat.fns["sd_colsum_chunks"](nb)) * C, dtype=torch.float32, device=pooled.device)
+    if film is not None:
+        gamma, beta, ipc, dgamma, dbeta, fpart = _film_bwd_args(film, Nb, H, W, C, pooled.device)
+        nat.call("sd_pool_rms_bwd_compact_film", p(pooled), p(amax), p(w), p(gamma), p(beta), ipc, p(rstd), p(_c(dy)),
+                 p(dp), p(dw), p(part), p(dgamma), p(dbeta), p(fpart), Nb, H, W, C, int(nchw_flat), 1, stream())
+        return dp, dgamma, dbeta
     nat.call("sd_pool_rms_bwd_compact", p(pooled), p(amax), p(w), p(rstd), p(_c(dy)), p(dp), p(dw), p(part), Nb, H, W,
              C, int(nchw_flat), 1, stream())
     return dp
 
 
-def pool_rms_bwd(pooled, amax, w, rstd, dy, H, W, dw, nchw_flat=False):
+def pool_rms_bwd(pooled, amax, w, rstd, dy, H, W, dw, nchw_flat=False, film=None):
+    """film = (gamma, beta): returns (dx, dgamma, dbeta)"""
     Nb, Ho, Wo, C = pooled.shape
     dx = torch.empty(Nb, H, W, C, dtype=torch.float32, device=pooled.device)
     nb = nat.fns["sd_pool_rms_bwd_blocks"](Nb, H, W)
     part = torch.empty((nb + nat.fns["sd_colsum_chunks"](nb)) * C, dtype=torch.float32, device=pooled.device)
+    if film is not None:
+        gamma, beta, ipc, dgamma, dbeta, fpart = _film_bwd_args(film, Nb, H, W, C, pooled.device)
+        nat.call("sd_pool_rms_bwd_film", p(pooled), p(amax), p(w), p(gamma), p(beta), ipc, p(rstd), p(_c(dy)), p(dx),
+                 p(dw), p(part), p(dgamma), p(dbeta), p(fpart), Nb, H, W, C, int(nchw_flat), 1, stream())
+        return dx, dgamma, dbeta
     nat.call("sd_pool_rms_bwd", p(pooled), p(amax), p(w), p(rstd), p(_c(dy)), p(dx), p(dw), p(part), Nb, H, W, C,
              int(nchw_flat), 1, stream())
     return dx
+
+
+# ------------------------------------------------------------------------------------------------- text conditioning
+def rowbias_silu_fwd(x, u=None, T=1):
+    """silu(x[n] + u[n // T]) over the rows of x (N, E); u (N // T, E) or None (plain SiLU)"""
+    x = _c(x)
+    N, E = x.shape
+    y = torch.empty_like(x)
+    if u is not None and u.shape != (N // T, E):
+        raise ValueError(f"row bias {tuple(u.shape)} for {N} rows in groups of {T}")
+    nat.call("sd_rowbias_silu_fwd", p(x), p(_c(u) if u is not None else None), p(y), N, E, int(T), stream())
+    return y
+
+
+def rowbias_silu_bwd(x, u, dy, T=1, need_du=True):
+    """-> (dx, du): du[b] = the sum of row b's T rows of dx (row order), None without u"""
+    N, E = x.shape
+    dx = torch.empty_like(x)
+    du = torch.empty_like(u) if (u is not None and need_du) else None
+    nat.call("sd_rowbias_silu_bwd", p(x), p(_c(u) if u is not None else None), p(_c(dy)), p(dx), p(du), N, E, int(T),
+             stream())
+    return dx, du
+
+
+def text_gate_fwd(v, a, tp, T):
+    """g = sigmoid(a); out = v + g * (tp[n // T] - v) -> (out, g); v, a (N, E), tp (N // T, E) never expanded"""
+    v, a, tp = _c(v), _c(a), _c(tp)
+    N, E = v.shape
+    if a.shape != (N, E) or tp.shape != (N // T, E) or N % T:
+        raise ValueError(f"text gate shapes: v {tuple(v.shape)}, a {tuple(a.shape)}, tp {tuple(tp.shape)}, T {T}")
+    out, g = torch.empty_like(v), torch.empty_like(v)
+    nat.call("sd_text_gate_fwd", p(v), p(a), p(tp), p(out), p(g), N, E, int(T), stream())
+    return out, g
+
+
+def text_gate_bwd(v, g, tp, d, T):
+    """-> (dv, da, dtp)"""
+    N, E = v.shape
+    dv, da, dtp = torch.empty_like(v), torch.empty_like(v), torch.empty_like(tp)
+    nat.call("sd_text_gate_bwd", p(v), p(g), p(tp), p(_c(d)), p(dv), p(da), p(dtp), N, E, int(T), stream())
+    return dv, da, dtp
+
+
+def text_pool(feats, w, bias, out=None):
+    """Attention pooling of token features (ntexts, ntok, D) or (ntok, D): softmax over tokens of f . w + bias,
+    weighted token sum -> (ntexts, D) (written into `out` when given)."""
+    f = _c(feats if feats.dim() == 3 else feats[None])
+    n, ntok, D = f.shape
+    out = torch.empty(n, D, dtype=torch.float32, device=f.device) if out is None else out
+    if not out.is_contiguous() or out.numel() != n * D:
+        raise ValueError("text_pool output must be a contiguous (ntexts, D) buffer")
+    nat.call("sd_text_pool", p(f), p(_c(w.reshape(-1))), p(bias), p(out), n, ntok, D, stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------- timeline marks

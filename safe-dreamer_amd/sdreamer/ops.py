@@ -192,12 +192,13 @@ class PairFirstFn(torch.autograd.Function):
 
 
 class RmsSiluFn(torch.autograd.Function):
-    """nn.RMSNorm(eps=1e-4) followed by SiLU (act=1) or nothing (act=0)."""
+    """nn.RMSNorm(eps=1e-4, or `eps`) followed by SiLU (act=1) or nothing (act=0). The backward reads the saved rstd,
+    so eps enters the forward only."""
 
     @staticmethod
-    def forward(ctx, x, w, act):
+    def forward(ctx, x, w, act, eps=None):
         x = x.contiguous()
-        y, rstd = k.rmsnorm_fwd(x, w, act=act)
+        y, rstd = k.rmsnorm_fwd(x, w, act=act, eps=eps)
         ctx.save_for_backward(x, w, rstd)
         ctx.act = act
         return y
@@ -207,7 +208,7 @@ class RmsSiluFn(torch.autograd.Function):
         x, w, rstd = ctx.saved_tensors
         dw = grad_buf(w) if w.requires_grad else None
         dx = k.rmsnorm_bwd(x, w, rstd, dy.contiguous(), act=ctx.act, dw=dw)
-        return dx, None, None
+        return dx, None, None, None
 
 
 class BlockLinearFn(torch.autograd.Function):
@@ -252,8 +253,8 @@ def linear_pre(h0, x, w, b=None):
     return LinearPreFn.apply(h0, x, w, b)
 
 
-def rms_silu(x, w, act=1):
-    return RmsSiluFn.apply(x, w, act)
+def rms_silu(x, w, act=1, eps=None):
+    return RmsSiluFn.apply(x, w, act, eps)
 
 
 def block_linear(x, wp, b):
@@ -351,6 +352,142 @@ class ConvPoolNormFn(torch.autograd.Function):
                 raise NotImplementedError("input gradient through a channel-padded conv")
             dx = k.conv2d_dgrad(dconv, w)
         return dx, None, None, None, None
+
+
+class FilmConvPoolNormFn(torch.autograd.Function):
+    """One FiLM encoder stage: Conv2dSamePad -> MaxPool2d(2) -> RMSNorm2D -> gamma * x + beta -> SiLU, NHWC, on
+    ConvPoolNormFn's kernels with the modulation in their epilogue. gamma / beta are (rows, Co), one row per
+    Nb / rows consecutive images (a batch row's T frames); their gradients are returned to autograd (the FiLM
+    generator continues the chain), every parameter gradient is accumulated as in ConvPoolNormFn. With gamma = 1 and
+    beta = 0 every output and gradient equals ConvPoolNormFn's bit for bit."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, nw, gamma, beta, nchw_flat):
+        wk = w if x.shape[-1] == w.shape[-1] else _pad_last(w, x.shape[-1])
+        film = (gamma.contiguous(), beta.contiguous())
+        fused = k.conv2d_fwd_pool(x.contiguous(), wk, b, nw, nchw_flat=nchw_flat, film=film) if FUSED_POOL else None
+        if fused is None:
+            conv = k.conv2d_fwd(x.contiguous(), wk, b)
+            fused = k.pool_rms_fwd(conv, nw, nchw_flat=nchw_flat, film=film)
+            del conv
+        y, pooled, amax, rstd = fused
+        ctx.save_for_backward(x, w, b, nw, pooled, amax, rstd, *film)
+        ctx.nchw_flat = nchw_flat
+        if nchw_flat:
+            return y.view(y.shape[0], -1)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b, nw, pooled, amax, rstd, gamma, beta = ctx.saved_tensors
+        Nb, H, W, _ = x.shape
+        Co, kh, kw, Ci = w.shape
+        acc = (grad_buf(w), grad_buf(b), Ci)
+        film = (gamma, beta)
+        if not ctx.needs_input_grad[0] and POOL_COMPACT and k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0:
+            dpool, dgamma, dbeta = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw),
+                                                          nchw_flat=ctx.nchw_flat, film=film)
+            k.conv2d_wgrad_pool(x, dpool, amax, kh, kw, acc=acc)
+            dconv = None
+        else:
+            dconv, dgamma, dbeta = k.pool_rms_bwd(pooled, amax, nw, rstd, dy.contiguous(), H, W, grad_buf(nw),
+                                                  nchw_flat=ctx.nchw_flat, film=film)
+
+        def wgrad():
+            k.conv2d_wgrad(x, dconv, kh, kw, acc=acc)
+
+        if dconv is None:
+            pass
+        elif _DEFER is not None:
+            _DEFER.append((wgrad, (x, dconv)))
+        else:
+            wgrad()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            if x.shape[-1] != Ci:
+                raise NotImplementedError("input gradient through a channel-padded conv")
+            dx = k.conv2d_dgrad(dconv, w)
+        return dx, None, None, None, dgamma, dbeta, None
+
+
+class RowBiasSiluFn(torch.autograd.Function):
+    """silu(x[n] + u[n // T]): x (N, E), u (N // T, E) or None (plain nn.SiLU). The text gate's first layer is
+    cat[v, tp] . W^T = v . Wv^T + (tp . Wt^T + b)[n // T]: the tp half is a B-row GEMM added here per batch row, so
+    neither the concatenation nor an expanded tp exists. du sums each batch row's T rows in row order."""
+
+    @staticmethod
+    def forward(ctx, x, u, T):
+        x = x.contiguous()
+        y = k.rowbias_silu_fwd(x, u, T)
+        ctx.save_for_backward(x, u)
+        ctx.T = T
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, u = ctx.saved_tensors
+        dx, du = k.rowbias_silu_bwd(x, u, dy.contiguous(), ctx.T, need_du=u is not None and ctx.needs_input_grad[1])
+        return dx, du, None
+
+
+class TextGateFn(torch.autograd.Function):
+    """out = (1 - g) v + g tp[n // T], g = sigmoid(a): v, a (N, E), tp (N // T, E) read by row n // T. Returns
+    (out, g); g carries no gradient (a diagnostic: its mean / unbiased std are Stat metrics)."""
+
+    @staticmethod
+    def forward(ctx, v, a, tp, T):
+        v, tp = v.contiguous(), tp.contiguous()
+        out, g = k.text_gate_fwd(v, a, tp, T)
+        ctx.save_for_backward(v, g, tp)
+        ctx.T = T
+        ctx.mark_non_differentiable(g)
+        return out, g
+
+    @staticmethod
+    def backward(ctx, d, _dg):
+        v, g, tp = ctx.saved_tensors
+        dv, da, dtp = k.text_gate_bwd(v, g, tp, d.contiguous(), ctx.T)
+        return dv, da, dtp, None
+
+
+class GateFirstFn(torch.autograd.Function):
+    """The text gate's first layer h = silu(cat[v, tp[n // T]] . W^T + b) without the concatenation: W (E, 2E) is read
+    as its v half and its tp half in place, pre = v . Wv^T over the N rows and u = tp . Wt^T + b over the B context
+    rows, h = silu(pre + u[n // T]). Forward on the exact f32 path (the posterior's input depends on it); the input
+    gradients and both halves of dW (accumulated into W's gradient in place) on the split-bf16 path."""
+
+    @staticmethod
+    def forward(ctx, v, tp, w, b, T):
+        E = w.shape[0]
+        v2, tp2 = v.contiguous(), tp.contiguous()
+        pre = k.mm(v2, w[:, :E].t())
+        u = k.mm(tp2, w[:, E:].t(), bias=b)
+        ctx.save_for_backward(v2, tp2, w, b, pre, u)
+        ctx.T = T
+        return k.rowbias_silu_fwd(pre, u, T)
+
+    @staticmethod
+    def backward(ctx, dh):
+        v2, tp2, w, b, pre, u = ctx.saved_tensors
+        E = w.shape[0]
+        dpre, du = k.rowbias_silu_bwd(pre, u, dh.contiguous(), ctx.T)
+        dv = k.mm(dpre, w[:, :E], fast=True) if ctx.needs_input_grad[0] else None
+        dtp = k.mm(du, w[:, E:], fast=True) if ctx.needs_input_grad[1] else None
+        if w.requires_grad:
+            gw = grad_buf(w)
+            k.wgrad(dpre, v2, gw[:, :E])
+            k.wgrad(du, tp2, gw[:, E:], grad_buf(b) if b.requires_grad else None)
+        elif b.requires_grad:
+            k.colsum(du, grad_buf(b), accumulate=True)
+        return dv, dtp, None, None, None
+
+
+def rowbias_silu(x, u=None, T=1):
+    return RowBiasSiluFn.apply(x, u, T)
+
+
+def text_gate(v, a, tp, T):
+    return TextGateFn.apply(v, a, tp, T)
 
 
 class UpConvFn(torch.autograd.Function):

@@ -102,6 +102,11 @@ class LaProp(torch.optim.Optimizer):
         self.agc, self.pmin = float(agc), float(pmin)
         self.warmup = float(warmup or 0)
         self.host_steps = 0
+        # checkpoint indices: state / param_groups index of arena parameter i in the reference's optimizer, and the
+        # reference's parameter count. Identity unless the reference's optimizer holds tensors this one does not (the
+        # multimodal text front end: in the reference's parameter list, never given a gradient, so never a state entry)
+        self.ref_index = list(range(len(self.arena.params)))
+        self.ref_count = len(self.arena.params)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -138,12 +143,12 @@ class LaProp(torch.optim.Optimizer):
                 continue
             lay = self.ref_layouts[i]
             view = (lambda t: t) if lay is None else lay[0]
-            st[i] = {"step": steps, "exp_avg": view(self.exp_avg[o:o + n].view(p.shape)).contiguous().clone(),
+            st[self.ref_index[i]] = {"step": steps, "exp_avg": view(self.exp_avg[o:o + n].view(p.shape)).contiguous().clone(),
                      "exp_avg_lr_1": float(sc[1]), "exp_avg_lr_2": float(sc[2]),
                      "exp_avg_sq": view(self.exp_avg_sq[o:o + n].view(p.shape)).contiguous().clone()}
         lr = self.current_lr()
         groups = [{"lr": lr, "betas": self.betas, "eps": self.eps, "weight_decay": 0, "amsgrad": False,
-                   "centered": False, "initial_lr": self.base_lr, "params": list(range(len(a.params)))}]
+                   "centered": False, "initial_lr": self.base_lr, "params": list(range(self.ref_count))}]
         return {"state": st, "param_groups": groups}
 
     def load_state_dict(self, sd, internal_layout=None):
@@ -154,7 +159,8 @@ class LaProp(torch.optim.Optimizer):
         st = sd.get("state", {})
         steps, e1, e2 = 0, 0.0, 0.0
         for i, (o, n) in enumerate(zip(a.offsets, a.sizes)):
-            s = st.get(i, st.get(str(i)))
+            j = self.ref_index[i]
+            s = st.get(j, st.get(str(j)))
             if not s:
                 continue
             lay, shape = self.ref_layouts[i], tuple(a.params[i].shape)
