@@ -245,63 +245,6 @@ struct DenseKCB {
   SD_DEV void store(float* lds) const { st.store(lds); }
 };
 
-// bwd-weight B operand, k-major: rows j = (ky, kx, ci) fixed per thread (decoded once), k = pixel (pow2 grid:
-// shifts). Consecutive lanes take consecutive 4-channel groups of one pixel -> coalesced 16-B loads.
-template <int ROWS>
-struct Im2colColsKM : KMajor<ROWS> {
-  using KMajor<ROWS>::r;
-  using KMajor<ROWS>::NV;
-  Geom G;
-  int J, lw, lhw;
-  int jc[NV], jy[NV], jx[NV], j0v[NV];  // jc < 0: the group straddles J (scalar path incl. the ones column)
-  SD_DEV Im2colColsKM(const Geom& g, int J_, int row0, int lw_, int lhw_) : G(g), J(J_), lw(lw_), lhw(lhw_) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int i = threadIdx.x + v * 256;
-      const int j0 = row0 + 4 * this->rq(i);
-      j0v[v] = j0;
-      jc[v] = -1;
-      jy[v] = jx[v] = 0;
-      if (j0 + 3 < J) {
-        const int t = j0 / G.C;
-        jc[v] = j0 - t * G.C;
-        jy[v] = t / G.kw - G.pad;
-        jx[v] = t - (t / G.kw) * G.kw - G.pad;
-      }
-    }
-  }
-  SD_DEV void load(int k0, int kend) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int i = threadIdx.x + v * 256;
-      f32x4 x = {0.f, 0.f, 0.f, 0.f};
-      const int m = k0 + this->kk(i);
-      if (i < ROWS * BK / 4 && m < kend && j0v[v] <= J) {
-        const int n = m >> lhw, rem = m & ((1 << lhw) - 1);
-        const int y = rem >> lw, xq = rem & ((1 << lw) - 1);
-        if (jc[v] >= 0) {
-          const int yy = y + jy[v], xx = xq + jx[v];
-          if (yy >= 0 && yy < G.Hg && xx >= 0 && xx < G.Wg)
-            x = *reinterpret_cast<const f32x4*>(
-                G.in + (((long)n * G.Hs + (yy >> G.ups)) * G.Ws + (xx >> G.ups)) * G.C + jc[v]);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int jj = j0v[v] + j;
-            long off;
-            if (jj < J) {
-              if (tap(G, n, y, xq, jj, off)) x[j] = G.in[off];
-            } else if (jj == J) {
-              x[j] = 1.f;
-            }
-          }
-        }
-      }
-      r[v] = x;
-    }
-  }
-};
-
 // fwd / bwd-data: M = pixels, N = Co (tile = all output channels), 16x16x4 MFMA, 4 waves along M
 template <int BN, bool ES>
 __global__ __launch_bounds__(256) void conv_fwd16(GemmArgs g, Geom G, int lw, int lhw) {
@@ -450,10 +393,10 @@ __global__ __launch_bounds__(256) void conv_fwd16_pool(GemmArgs g, Geom G, int l
 // fragments are read from it at the tap's offset — the 25x im2col expansion is never re-read from L2. The weights
 // stream through a double-buffered early-store B stage, one (tap, 32-channel) k tile per iteration; the epilogue
 // (pool + RMSNorm + SiLU) is conv_fwd16_pool's, staged in the patch area. Wave w owns tile pixels 32w..32w+31
-// (TM = 2) x all BN channels. A workgroup runs TPW vertically adjacent tiles (XCD-aware order: an XCD's workgroups
-// cover a contiguous tile range, so the KS - 1 halo rows adjacent tiles share are L2 hits), loading the next tile's
-// patch into registers under the current tile's MFMAs.
-template <int BN, int CI, int LW, int KS, int TPW, class NW = const float*>
+// (TM = 2) x all BN channels. One tile per workgroup, in XCD-aware order: an XCD's workgroups cover a contiguous tile
+// range, so the KS - 1 halo rows adjacent tiles share are L2 hits. (Workgroups running 2 or 4 vertically adjacent
+// tiles, the next tile's patch loaded into registers under the current tile's MFMAs, were built and not kept.)
+template <int BN, int CI, int LW, int KS, class NW = const float*>
 __global__ __launch_bounds__(256) void conv_fwd_direct_pool(GemmArgs g, Geom G, int lhw, NW nw,
                                                             float* pooled, uint8_t* amax, float* y, float* rstd,
                                                             float eps, int nchw_flat) {
@@ -492,60 +435,56 @@ __global__ __launch_bounds__(256) void conv_fwd_direct_pool(GemmArgs g, Geom G, 
     abase[i] = ((p >> LW) * PW + (p & (W - 1))) * CSI + 8 * q;
   }
   DenseKCB<BN> lb(g.B, g.ldb, g.N, 0);
-  load_patch(wg * TPW);
-  for (int it = 0; it < TPW; ++it) {
-    const int tile = wg * TPW + it;
-    if (tile >= ntiles) break;  // uniform over the workgroup
-    if (it > 0) __syncthreads();  // the previous tile's epilogue is done with the patch area
-    lb.load(0, g.K);
+  const int tile = wg;
+  load_patch(tile);
+  if (tile >= ntiles) return;  // uniform over the workgroup
+  lb.load(0, g.K);
 #pragma unroll
-    for (int u = 0; u < NQT; ++u) {
-      const int i = threadIdx.x + 256 * u;
-      if ((u + 1) * 256 <= NQ || i < NQ)
-        *reinterpret_cast<f32x4*>(patch + (i / (CI / 4)) * CSI + 4 * (i % (CI / 4))) = v[u];
-    }
-    lb.store(bst);
-    lb.load(BK, g.K);
-    __syncthreads();
-    if (it + 1 < TPW) load_patch(tile + 1);
-    f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt < NK; ++kt) {
-      const float* cur = bst + (kt & 1) * SB;
-      float* nxt = bst + ((kt & 1) ^ 1) * SB;
-      const int tap = kt / (CI / BK), ci0 = (kt % (CI / BK)) * BK;
-      const int toff = ((tap / KS) * PW + tap % KS) * CSI + ci0;
-      float af[TM][8], bf[TN][8];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const float* pa = patch + abase[i] + toff;
-        const f32x4 x0 = *reinterpret_cast<const f32x4*>(pa), x1 = *reinterpret_cast<const f32x4*>(pa + 4);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { af[i][s] = x0[s]; af[i][4 + s] = x1[s]; }
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const float* pb = cur + (16 * j + l16) * LDS_ROW + 8 * q;
-        const f32x4 x0 = *reinterpret_cast<const f32x4*>(pb), x1 = *reinterpret_cast<const f32x4*>(pb + 4);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { bf[j][s] = x0[s]; bf[j][4 + s] = x1[s]; }
-      }
-      lb.store(nxt);
-      lb.load((kt + 2 < NK ? kt + 2 : NK - 1) * BK, g.K);
-#pragma unroll
-      for (int s = 0; s < 8; ++s)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][s], bf[j][s], acc[i][j], 0, 0, 0);
-      __syncthreads();
-    }
-    pool_epilogue<BN, WM>(acc, patch, g, G, LW, lhw, tile * BM, nw, pooled, amax, y, rstd, eps, nchw_flat);
+  for (int u = 0; u < NQT; ++u) {
+    const int i = threadIdx.x + 256 * u;
+    if ((u + 1) * 256 <= NQ || i < NQ)
+      *reinterpret_cast<f32x4*>(patch + (i / (CI / 4)) * CSI + 4 * (i % (CI / 4))) = v[u];
   }
+  lb.store(bst);
+  lb.load(BK, g.K);
+  __syncthreads();
+  f32x4 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kt = 0; kt < NK; ++kt) {
+    const float* cur = bst + (kt & 1) * SB;
+    float* nxt = bst + ((kt & 1) ^ 1) * SB;
+    const int tap = kt / (CI / BK), ci0 = (kt % (CI / BK)) * BK;
+    const int toff = ((tap / KS) * PW + tap % KS) * CSI + ci0;
+    float af[TM][8], bf[TN][8];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const float* pa = patch + abase[i] + toff;
+      const f32x4 x0 = *reinterpret_cast<const f32x4*>(pa), x1 = *reinterpret_cast<const f32x4*>(pa + 4);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) { af[i][s] = x0[s]; af[i][4 + s] = x1[s]; }
+    }
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const float* pb = cur + (16 * j + l16) * LDS_ROW + 8 * q;
+      const f32x4 x0 = *reinterpret_cast<const f32x4*>(pb), x1 = *reinterpret_cast<const f32x4*>(pb + 4);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) { bf[j][s] = x0[s]; bf[j][4 + s] = x1[s]; }
+    }
+    lb.store(nxt);
+    lb.load((kt + 2 < NK ? kt + 2 : NK - 1) * BK, g.K);
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][s], bf[j][s], acc[i][j], 0, 0, 0);
+    __syncthreads();
+  }
+  pool_epilogue<BN, WM>(acc, patch, g, G, LW, lhw, tile * BM, nw, pooled, amax, y, rstd, eps, nchw_flat);
 }
 
 // conv_fwd_direct_pool on the fp32-accurate three-way split-bf16 path (gemm6_core.h: a = a0 + a1 + a2, six
@@ -659,38 +598,37 @@ __global__ __launch_bounds__(256, 2) void conv_fwd6_direct_pool(GemmArgs g, Geom
 // double-buffered LDS ring shared by the 8 waves (conv_dgrad3_direct's ring, three planes) instead of every lane loading
 // its own fragments from L2 (0.9 MB of weight per 128-pixel tile: the L2 -> CU path bound the kernel, MFMA busy 0.37).
 // Same products in the same k order: bit-identical to conv_fwd6_direct_pool.
-// CG: the patch planes channel-group-major ([plane][CI / 8][PH * PW][8] bf16) instead of pixel-major with a pad: the 16
+// The patch planes are channel-group-major ([plane][CI / 8][PH * PW][8] bf16), not pixel-major with a pad: the 16
 // lanes of a fragment read 16 consecutive pixels' 16-B pieces (conflict-free with no pad), so the 48 -> 64 stage's
-// whole-image 256-pixel tile (20 x 20 x 48 patch) fits beside the ring (146 KB; pixel-major with its pad is 165 KB).
-// PIPE: the fragments of chunk kc + 1 are read from LDS into a second register set under chunk kc's MFMAs (the ring
-// stage chunk kc + 2 goes to is the one every wave finished reading before the previous barrier), so the LDS read
-// latency is no longer exposed once per chunk; one barrier per chunk either way, same products in the same order.
+// whole-image 256-pixel tile (20 x 20 x 48 patch) fits beside the ring (146 KB; pixel-major with its pad was 165 KB).
+// (The 32 -> 48 stage ran pixel-major on 256-pixel tiles until its 512-pixel tiles, below, took the same layout.)
+// Tried and retired: a fragment register pipeline (chunk kc + 1's fragments read from LDS into a second register set
+// under chunk kc's MFMAs, so that the LDS read latency was not exposed once per chunk) measured 1 % faster alone
+// (profiles/r06s3b) but spilled together with the patch prefetch, and lost to the multi-tile workgroups.
 // TPW: a workgroup runs TPW consecutive tiles (XCD-contiguous ranges, so the halo rows adjacent tiles share are L2
 // hits), the next tile's patch loaded into registers under this tile's MFMAs and the ring's first chunk under its
 // epilogue: with one workgroup per CU the prologue's HBM round trip was otherwise exposed once per tile.
 // MT: 16-pixel m tiles per wave (2: 256-pixel tiles; 4: 512-pixel tiles, each wave 64 pixels x BN channels — 21
 // fragment reads per 72 MFMAs instead of 15 per 36: less LDS traffic per product). BROW: the ring's row stride in bf16
 // (40 = 32 + a pad; 32 = packed, the 64-B rows of a fragment read are still 1 KB contiguous).
-// NTH: threads (the 48 -> 64 stage's whole image as four 64-pixel waves on 256 threads measured slower than eight
+// 512 threads (the 48 -> 64 stage's whole image as four 64-pixel waves on 256 threads measured slower than eight
 // 32-pixel waves, 213.7 vs 180.5 us, profiles/r06m3: one wave per SIMD).
-template <int BN, int CI, int LW, int KS, bool CG, bool PIPE, int TPW, int MT = 2, int BROW = 40, int NTH = 512,
-          class NW = const float*>
-__global__ __launch_bounds__(NTH, 1) void conv_fwd6r_direct_pool(GemmArgs g, Geom G, int lhw,
+template <int BN, int CI, int LW, int KS, int TPW, int MT = 2, int BROW = 40, class NW = const float*>
+__global__ __launch_bounds__(512, 1) void conv_fwd6r_direct_pool(GemmArgs g, Geom G, int lhw,
                                                                   const __bf16* __restrict__ wsp, NW nw,
                                                                   float* pooled, uint8_t* amax, float* y, float* rstd,
                                                                   float eps, int nchw_flat) {
-  constexpr int TP = 16 * MT * (NTH / 64);
-  static_assert(!PIPE || MT == 2, "the fragment pipeline is built for two m tiles");
-  constexpr int W = 1 << LW, R = TP / W, PH = R + KS - 1, PW = W + KS - 1, CP = CG ? CI : CI + 8, PAD = KS / 2;
-  constexpr int NPIX = PH * PW, PLANE = NPIX * CP, K = KS * KS * CI, NKC = (K + 31) / 32, KP = NKC * 32, TN = BN / 16;
+  constexpr int NTH = 512, TP = 16 * MT * (NTH / 64);
+  constexpr int W = 1 << LW, R = TP / W, PH = R + KS - 1, PW = W + KS - 1, PAD = KS / 2;
+  constexpr int NPIX = PH * PW, PLANE = NPIX * CI, K = KS * KS * CI, NKC = (K + 31) / 32, KP = NKC * 32, TN = BN / 16;
   constexpr int CI4 = CI / 4, NEL = PH * PW * CI4, NE = (NEL + NTH - 1) / NTH;
   constexpr int SB = 3 * BN * BROW, NPC = 3 * BN * 4, NPT = (NPC + NTH - 1) / NTH;  // ring: [plane][n][BROW]
   // element offset of (pixel, channel c, c % 4 == 0) in a plane
-  auto poff = [](int pix, int c) { return CG ? ((c >> 3) * NPIX + pix) * 8 + (c & 7) : pix * CP + c; };
+  auto poff = [](int pix, int c) { return ((c >> 3) * NPIX + pix) * 8 + (c & 7); };
   static_assert(CI % 8 == 0 && TP % W == 0 && BN % 16 == 0, "geometry");
   static_assert(TP * (BN + 1) * 4 <= 3 * PLANE * 2, "epilogue tile fits the patch area");
   typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-  extern __shared__ __attribute__((aligned(16))) __bf16 patch6r[];  // [plane][PH][PW][CP], then the ring [2][SB]
+  extern __shared__ __attribute__((aligned(16))) __bf16 patch6r[];  // [plane][CI / 8][NPIX][8], then the ring [2][SB]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, q = lane >> 4;
   const int nwg = gridDim.x, ntiles = g.M / TP;
   const int wg = (nwg & 7) ? blockIdx.x : (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
@@ -762,54 +700,6 @@ __global__ __launch_bounds__(NTH, 1) void conv_fwd6r_direct_pool(GemmArgs g, Geo
     for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
   if (it + 1 < TPW) load_patch(tile + 1);
-  if constexpr (PIPE) {
-    bf16x8 a[2][2][3], b[2][TN][3];
-    auto frag = [&](int kc, int s) {  // chunk kc's fragments (ring stage kc & 1, the patch) into register set s
-      const __bf16* bs = bst + (kc & 1) * SB + l16 * BROW + 8 * q;
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          b[s][j][pl] = *reinterpret_cast<const bf16x8*>(bs + (pl * BN + 16 * j) * BROW);
-      int k0 = 32 * kc + 8 * q;
-      k0 = k0 < K ? k0 : K - 8;  // past K: any in-patch address (the weight is zero there)
-      const int tap = k0 / CI, c0 = k0 - tap * CI, ky = tap / KS, kx = tap - ky * KS;
-      const int toff = ky * PW + kx;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          a[s][mt][pl] = *reinterpret_cast<const bf16x8*>(patch6r + pl * PLANE + poff(pbase[mt] + toff, c0));
-    };
-    frag(0, 0);
-    if (NKC > 1) bstore(1);  // chunk 1 (in br) into stage 1
-    if (NKC > 2) bload(2);
-    __syncthreads();  // chunk 1 visible; every wave's chunk-0 reads are done
-    auto step = [&](int kc, int s) {  // register set s holds chunk kc; stage (kc + 1) & 1 holds chunk kc + 1
-      if (kc + 1 < NKC) frag(kc + 1, s ^ 1);
-      if (kc + 2 < NKC) bstore(kc & 1);  // chunk kc + 2 (in br) over chunk kc, read before the last barrier
-      if (kc + 3 < NKC) bload(kc + 3);
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          f32x4 c = acc[mt][j];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s][mt][2], b[s][j][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s][mt][1], b[s][j][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s][mt][0], b[s][j][2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s][mt][1], b[s][j][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s][mt][0], b[s][j][1], c, 0, 0, 0);
-          acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s][mt][0], b[s][j][0], c, 0, 0, 0);
-        }
-      __syncthreads();
-    };
-    int kc = 0;
-    for (; kc + 2 <= NKC; kc += 2) {
-      step(kc, 0);
-      step(kc + 1, 1);
-    }
-    if (kc < NKC) step(kc, 0);
-  } else
   for (int kc = 0; kc < NKC; ++kc) {
     const __bf16* bs = bst + (kc & 1) * SB + l16 * BROW + 8 * q;
     bf16x8 b[TN][3];
@@ -952,30 +842,8 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_direct_pool_c4(GemmArgs g, 
   }
 }
 
-// SDHIP_CONV_DIRECT_FWD (benchmarking knob): 1 (default) = conv_fwd_direct_pool where it applies, 0 = implicit GEMM.
-// (A variant streaming each lane's weight fragments into registers — no LDS stage, no barriers, 3 workgroups per
-// CU — measured slower: 679 vs 660 us on encoder stage 2 at 1024 images.)
-bool conv_direct_fwd() {
-  static int a = -1;
-  if (a < 0) {
-    const char* e = getenv("SDHIP_CONV_DIRECT_FWD");
-    a = e ? atoi(e) : 1;
-  }
-  return a != 0;
-}
-
-// bwd-weight: M = Co (one tile), N = kh*kw*Ci + 1, K = pixels (split-K slabs), 4 waves along N
-template <int BM>
-__global__ __launch_bounds__(256) void conv_wgrad16(GemmArgs g, Geom G, int J, int lw, int lhw) {
-  constexpr int BN = 128;
-  const int bn0 = blockIdx.x * BN;
-  const int split = blockIdx.z;
-  const int kbeg = split * g.kchunk;
-  const int kend = min(g.K, kbeg + g.kchunk);
-  DenseKM<BM, true> la(g.A, g.lda, g.M, 0);
-  Im2colColsKM<BN> lb(G, J, bn0, lw, lhw);
-  gemm_block16<BM, BN, BM, 32>(g, la, lb, 0, bn0, 0, split, kbeg, kend);
-}
+// (A variant of conv_fwd_direct_pool streaming each lane's weight fragments into registers, with no LDS stage, no
+// barriers and 3 workgroups per CU, measured slower: 679 vs 660 us on encoder stage 2 at 1024 images.)
 
 // ---------------------------------------------------------------- direct bwd-weight (stride 1, no upsample)
 // dW[co][j = (ky,kx,ci)] (+ d bias at j = J) = sum over pixels of dy[p][co] * x[p + (ky,kx) - pad][ci].
@@ -1204,21 +1072,23 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad3(GemmArgs g, Geom G, int lw
 // per plane), one k chunk ahead. M = R*W output pixels per workgroup (128), 4 waves x 2 16-pixel tiles, NT 16-channel
 // tiles of dIn; per 32-deep k chunk a lane's 8 k values are 8 consecutive channels of one tap (CIN % 8 == 0), one
 // ds_read_b128 per plane. Products: lo_a*hi_b + hi_a*lo_b + hi_a*hi_b (gemm3_mainloop's order), f32 accumulation.
-// MT / CG / NTHR (round 6): MT 16-pixel m tiles per wave over NTHR threads (the tile is 16 MT NTHR / 64 pixels), the
-// patch channel-group-major when CG ([plane][CIN / 8][pixel][8]: no pad, conflict-free), as conv_fwd6r_direct_pool's
-// 64-pixel waves: 12 fragment reads per 24 MFMAs instead of 8 per 12. Same products in the same k order.
-template <int CIN, int NT, int LW, int KS, int MT = 2, bool CG = false, int NTHR = 256>
+// Round 6: MT = 4 16-pixel m tiles per wave over NTHR threads (the tile is 64 NTHR / 64 pixels), the patch
+// channel-group-major ([plane][CIN / 8][pixel][8]: no pad, conflict-free), as conv_fwd6r_direct_pool's 64-pixel
+// waves: 12 fragment reads per 24 MFMAs instead of 8 per 12. Same products in the same k order. The first form, 128-pixel
+// tiles of 32-pixel waves (MT = 2) with a padded pixel-major patch, two workgroups per CU, was retired: 183 -> 131 us
+// alone on the 64 -> 48 stage (profiles/r06dg3).
+template <int CIN, int NT, int LW, int KS, int NTHR>
 __global__ __launch_bounds__(NTHR, 2) void conv_dgrad3_direct(const float* __restrict__ dout,
                                                                const __bf16* __restrict__ wsp, float* __restrict__ din,
                                                                int Nb, int H, int pad) {
-  constexpr int TP = 16 * MT * (NTHR / 64);
-  constexpr int W = 1 << LW, R = TP / W, PH = R + KS - 1, PW = W + KS - 1, CP = CG ? CIN : CIN + 8, NPIX = PH * PW;
-  constexpr int PLANE = PH * PW * CP, K = KS * KS * CIN, NKC = (K + 31) / 32, KP = NKC * 32, NOUT = 16 * NT;
+  constexpr int MT = 4, TP = 16 * MT * (NTHR / 64);
+  constexpr int W = 1 << LW, R = TP / W, PH = R + KS - 1, PW = W + KS - 1, NPIX = PH * PW;
+  constexpr int PLANE = NPIX * CIN, K = KS * KS * CIN, NKC = (K + 31) / 32, KP = NKC * 32, NOUT = 16 * NT;
   constexpr int CIN4 = CIN / 4, NEL = PH * PW * CIN4, NE = (NEL + NTHR - 1) / NTHR;
   static_assert(CIN % 8 == 0 && R >= 1 && TP % W == 0, "geometry");
   // element offset of (pixel, channel c, c % 4 == 0) in a plane
-  auto poff = [](int pix, int c) { return CG ? ((c >> 3) * NPIX + pix) * 8 + (c & 7) : pix * CP + c; };
-  extern __shared__ __attribute__((aligned(16))) __bf16 patch[];  // [plane][PH][PW][CP]
+  auto poff = [](int pix, int c) { return ((c >> 3) * NPIX + pix) * 8 + (c & 7); };
+  extern __shared__ __attribute__((aligned(16))) __bf16 patch[];  // [plane][CIN / 8][NPIX][8]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, q = lane >> 4;
   const int rows_per_img = H / R, n = blockIdx.x / rows_per_img, y0 = (blockIdx.x % rows_per_img) * R;
   // stage the patch: every load first, then split + store
@@ -1252,7 +1122,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv_dgrad3_direct(const float* __res
     pbase[mt] = (p >> LW) * PW + (p & (W - 1));
   }
   // B: one k chunk of the pre-split weight ([plane][NOUT][32] bf16, 16-B pieces) per LDS stage, double-buffered and
-  // shared by the 4 waves (each wave reading its fragments from global memory itself made the L1 path the bound)
+  // shared by the waves (each wave reading its fragments from global memory itself made the L1 path the bound)
   typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
   constexpr int BROW = 40, SB = 2 * NOUT * BROW, NPC = 8 * NOUT, NPT = (NPC + NTHR - 1) / NTHR;
   __bf16* bst = patch + 2 * PLANE;
@@ -1390,13 +1260,10 @@ struct DirectW3 {
   int J, PW, PH, CP, PS, blocks;
 };
 
-// SD_WD3_PRE (default 1): the input patch is staged PRE-SPLIT, each element as one 32-bit word (bf16 hi in the low
-// half, bf16 lo in the high half: the same split2 values), so the inner loop forms a lane's 8 B-values of each plane
-// with 4 v_perm_b32 instead of re-splitting 8 floats per use (every patch element feeds kh * kw taps x the column
-// blocks): bit-identical products, the split VALU moved from the k loop to the stage.
-#ifndef SD_WD3_PRE
-#define SD_WD3_PRE 1
-#endif
+// The input patch is staged PRE-SPLIT, each element as one 32-bit word (bf16 hi in the low half, bf16 lo in the high
+// half: the same split2 values), so the inner loop forms a lane's 8 B-values of each plane with 4 v_perm_b32. (The
+// first form staged f32 and re-split 8 floats per use, and every patch element feeds kh * kw taps x the column
+// blocks: bit-identical products, the split VALU moved from the k loop to the stage.)
 SD_DEV uint32_t pack_split(float v) {  // (bf16 hi | bf16 lo << 16), hi + lo = v up to 2^-17 |v| (split2's values)
   const f32x4 x = {v, 0.f, 0.f, 0.f};
   sdb::bf16x4 hi, lo;
@@ -1502,29 +1369,20 @@ __global__ __launch_bounds__(512) void conv_wgrad3_direct(DirectW3 d) {
       const int i = tid + 512 * v;
       if (i < nP) {
         const int pix = i / cq, c = 4 * (i - pix * cq);
-        if (SD_WD3_PRE) {
-          sdb::bf16x4 hi, lo;
-          sdb::split2(rp[v], hi, lo);
-          const uint64_t h = __builtin_bit_cast(uint64_t, hi), l = __builtin_bit_cast(uint64_t, lo);
-          typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-          u32x4_ w;
+        sdb::bf16x4 hi, lo;
+        sdb::split2(rp[v], hi, lo);
+        const uint64_t h = __builtin_bit_cast(uint64_t, hi), l = __builtin_bit_cast(uint64_t, lo);
+        typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
+        u32x4_ w;
 #pragma unroll
-          for (int k = 0; k < 4; ++k) w[k] = (uint32_t)((h >> (16 * k)) & 0xffffu) | ((uint32_t)((l >> (16 * k)) & 0xffffu) << 16);
-          *reinterpret_cast<u32x4_*>(xp + pix * d.CP + c) = w;
-        } else {
-          *reinterpret_cast<f32x4*>(xp + pix * d.CP + c) = rp[v];
-        }
+        for (int k = 0; k < 4; ++k) w[k] = (uint32_t)((h >> (16 * k)) & 0xffffu) | ((uint32_t)((l >> (16 * k)) & 0xffffu) << 16);
+        *reinterpret_cast<u32x4_*>(xp + pix * d.CP + c) = w;
       }
     }
   };
   for (int pix = tid; pix < d.PH * d.PW; pix += 512) {
-    if (SD_WD3_PRE) {
-      reinterpret_cast<uint32_t*>(xp)[pix * d.CP + d.Ci] = pack_split(1.f);
-      reinterpret_cast<uint32_t*>(xp)[pix * d.CP + d.Ci + 1] = 0u;
-    } else {
-      xp[pix * d.CP + d.Ci] = 1.f;
-      xp[pix * d.CP + d.Ci + 1] = 0.f;
-    }
+    reinterpret_cast<uint32_t*>(xp)[pix * d.CP + d.Ci] = pack_split(1.f);
+    reinterpret_cast<uint32_t*>(xp)[pix * d.CP + d.Ci + 1] = 0u;
   }
   int rb = blockIdx.y;
   if (rb < d.blocks) fetch(rb);
@@ -1549,30 +1407,19 @@ __global__ __launch_bounds__(512) void conv_wgrad3_direct(DirectW3 d) {
       }
 #pragma unroll
       for (int b = 0; b < NBW; ++b) {
-        sdb::bf16x8 bh, bl;
-        if (SD_WD3_PRE) {  // 8 packed words -> the two planes, 2 elements per v_perm_b32
-          const uint32_t* xu = reinterpret_cast<const uint32_t*>(xp);
-          uint32_t wv[8];
+        // 8 packed words -> the two planes, 2 elements per v_perm_b32
+        const uint32_t* xu = reinterpret_cast<const uint32_t*>(xp);
+        uint32_t wv[8];
 #pragma unroll
-          for (int i = 0; i < 8; ++i) wv[i] = xu[pb[i] + off[b]];
-          typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-          u32x4_ ph, pl;
+        for (int i = 0; i < 8; ++i) wv[i] = xu[pb[i] + off[b]];
+        typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
+        u32x4_ ph, pl;
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            ph[i] = __builtin_amdgcn_perm(wv[2 * i + 1], wv[2 * i], 0x05040100u);  // lo halves: the hi plane
-            pl[i] = __builtin_amdgcn_perm(wv[2 * i + 1], wv[2 * i], 0x07060302u);  // hi halves: the lo plane
-          }
-          bh = __builtin_bit_cast(sdb::bf16x8, ph);
-          bl = __builtin_bit_cast(sdb::bf16x8, pl);
-        } else {
-          const f32x4 v0 = {xp[pb[0] + off[b]], xp[pb[1] + off[b]], xp[pb[2] + off[b]], xp[pb[3] + off[b]]};
-          const f32x4 v1 = {xp[pb[4] + off[b]], xp[pb[5] + off[b]], xp[pb[6] + off[b]], xp[pb[7] + off[b]]};
-          sdb::bf16x4 h0, h1, e0, e1;
-          sdb::split2(v0, h0, e0);
-          sdb::split2(v1, h1, e1);
-          bh = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-          bl = __builtin_shufflevector(e0, e1, 0, 1, 2, 3, 4, 5, 6, 7);
+        for (int i = 0; i < 4; ++i) {
+          ph[i] = __builtin_amdgcn_perm(wv[2 * i + 1], wv[2 * i], 0x05040100u);  // lo halves: the hi plane
+          pl[i] = __builtin_amdgcn_perm(wv[2 * i + 1], wv[2 * i], 0x07060302u);  // hi halves: the lo plane
         }
+        const sdb::bf16x8 bh = __builtin_bit_cast(sdb::bf16x8, ph), bl = __builtin_bit_cast(sdb::bf16x8, pl);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           acc[i][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh, acc[i][b], 0, 0, 0);
@@ -1616,27 +1463,6 @@ __global__ __launch_bounds__(512) void conv_wgrad3_direct(DirectW3 d) {
         }
     }
   }
-}
-
-// SDHIP_CONV_ALGO (benchmarking knob): 0 = auto, 1 = 32x32-tile kernels only, 2 = 16x16 kernels where eligible
-int conv_algo() {
-  static int a = -1;
-  if (a < 0) {
-    const char* e = getenv("SDHIP_CONV_ALGO");
-    a = e ? atoi(e) : 0;
-  }
-  return a;
-}
-
-// SDHIP_CONV_ES (benchmarking knob): 1 (default) = 16x16 conv kernels on the early-store main loop with buffer-load
-// operands, 0 = the double-buffered main loop with branchy loaders
-bool conv_es() {
-  static int a = -1;
-  if (a < 0) {
-    const char* e = getenv("SDHIP_CONV_ES");
-    a = e ? atoi(e) : 1;
-  }
-  return a != 0;
 }
 
 int ilog2_exact(int v) {  // log2(v) if v is a power of two, else -1
@@ -1925,22 +1751,14 @@ int patch_stride(int Ci) {  // >= Ci + 2 (ones / zero channels), % 4 == 0, 16 or
 }
 
 // pixels per staged row block of the max-pool-fused f32 direct bwd-weight (encoder first stage): more pixels per
-// block = more MFMA steps per barrier (128 / 256 / 512 px: 397 / 337 / 305 us at 1024 images; default 512, falling
-// back to smaller blocks where the staging does not fit, pool_plan); SDHIP_WGRAD_PIX overrides
-int wgrad_pool_pix() {
-  static int a = -1;
-  if (a < 0) {
-    const char* e = getenv("SDHIP_WGRAD_PIX");
-    a = e ? atoi(e) : 512;
-    if (a < 1) a = 512;
-  }
-  return a;
-}
+// block = more MFMA steps per barrier (128 / 256 / 512 px: 397 / 337 / 305 us at 1024 images), falling back to
+// smaller blocks where the staging does not fit (pool_plan)
+constexpr int WGRAD_POOL_PIX = 512;
 
 // pool_pix > 0: dy arrives at pooled resolution (a quarter of the block's pixels are fetched), blocks of pool_pix px
 bool direct_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, int ups, DirectPlan& pl, int pool_pix = 0) {
   const bool pool = pool_pix > 0;
-  if (conv_algo() != 0 || ups != 0 || Co % 16 || Co > 64 || Ci % 4 || ilog2_exact(W) < 0) return false;
+  if (ups != 0 || Co % 16 || Co > 64 || Ci % 4 || ilog2_exact(W) < 0) return false;
   const int pix = pool ? pool_pix : 128;
   pl.R = W >= pix ? 1 : (pix / W < H ? pix / W : H);
   if (H % pl.R || (pl.R * W) % 4) return false;
@@ -2019,10 +1837,11 @@ extern "C" int sd_conv2d_fwd(const float* in, const float* w, const float* bias,
   const bool vb = (((long)kh * kw * Ci) % 4 == 0) && al16(w);
   const bool va = (Ci % 4 == 0) && al16(in) && vb;
   const int lw = ilog2_exact(G.Wg), lhw = ilog2_exact(G.Hg * G.Wg);
-  if (conv_algo() != 1 && va && lw >= 0 && lhw >= 0 && g.K / 4 <= MAX_TAPQ &&
-      (Co == 32 || Co == 48 || Co == 64 || Co == 16)) {
+  if (va && lw >= 0 && lhw >= 0 && g.K / 4 <= MAX_TAPQ && (Co == 32 || Co == 48 || Co == 64 || Co == 16)) {
     const dim3 grid(sd_cdiv(g.M, 128));
-    const bool es = conv_es() && (long)Nb * Hs * Ws * Ci < (1L << 29);  // buffer offsets < 2 GiB
+    // the early-store main loop with buffer-load operands while every buffer offset is < 2 GiB, else the
+    // double-buffered main loop with branchy loaders
+    const bool es = (long)Nb * Hs * Ws * Ci < (1L << 29);
 #define SD_FWD16(BN) (es ? conv_fwd16<BN, true><<<grid, 256, 0, s>>>(g, G, lw, lhw) \
                          : conv_fwd16<BN, false><<<grid, 256, 0, s>>>(g, G, lw, lhw))
     switch (Co) {
@@ -2054,35 +1873,19 @@ static int fwd_pool_impl(const float* in, const float* w, const float* bias, NW 
   const bool vb = (((long)kh * kw * Ci) % 4 == 0) && al16(w);
   const bool va = (Ci % 4 == 0) && al16(in) && vb;
   const int lw = ilog2_exact(Ws), lhw = ilog2_exact(Hs * Ws);
-  if (conv_algo() == 1 || !va || lw < 1 || lhw < 0 || g.K / 4 > MAX_TAPQ || Hs % 2 || 128 % (2 * Ws) ||
-      g.M % 128)
-    return SD_ESHAPE;
+  if (!va || lw < 1 || lhw < 0 || g.K / 4 > MAX_TAPQ || Hs % 2 || 128 % (2 * Ws) || g.M % 128) return SD_ESHAPE;
   const dim3 grid(g.M / 128);
-  const bool es = conv_es() && (long)Nb * Hs * Ws * Ci < (1L << 29);  // buffer offsets < 2 GiB
-  if (conv_direct_fwd() && es && Co == 48 && Ci == 32 && Ws == 32 && kh == 5 && kw == 5 && pad == 2 &&
-      Hs % 4 == 0 && al16(in)) {
-    const char* e = getenv("SDHIP_C32_TPW");
-    const int tpw = e ? atoi(e) : 1;
-#define SD_C32(TPW)                                                                                                \
-  conv_fwd_direct_pool<48, 32, 5, 5, TPW, NW><<<sd_cdiv(g.M / 128, TPW), 256, 0, s>>>(g, G, lhw, nw, pooled, amax, \
-                                                                                     y, rstd, eps, nchw_flat)
-    if (tpw == 4) SD_C32(4);
-    else if (tpw == 1) SD_C32(1);
-    else SD_C32(2);
-#undef SD_C32
+  const bool es = (long)Nb * Hs * Ws * Ci < (1L << 29);  // buffer offsets < 2 GiB
+  if (es && Co == 48 && Ci == 32 && Ws == 32 && kh == 5 && kw == 5 && pad == 2 && Hs % 4 == 0 && al16(in)) {
+    conv_fwd_direct_pool<48, 32, 5, 5, NW><<<g.M / 128, 256, 0, s>>>(g, G, lhw, nw, pooled, amax, y, rstd, eps,
+                                                                     nchw_flat);
     SD_LAUNCH_CHECK();
     return SD_OK;
   }
-  if (conv_direct_fwd() && es && Co == 32 && Ci == 4 && Ws == 64 && kh == 5 && kw == 5 && pad == 2 &&
-      Hs % 2 == 0 && al16(in)) {
-    // SDHIP_C4_TPW = n > 0: n tiles per workgroup (the round-5 default was 16: 2048 workgroups, 2.67 rounds of
-    // the 768 then resident); default 0 = one round of resident workgroups (SDHIP_C4_OCC per CU, default 4).
-    const char* e = getenv("SDHIP_C4_TPW");
-    const char* eo = getenv("SDHIP_C4_OCC");
-    const int occ = eo ? atoi(eo) : 4, tiles = g.M / 128;
-    int tpw = e ? atoi(e) : 0;
-    if (tpw <= 0) tpw = sd_cdiv(tiles, 256 * (occ > 0 ? occ : 4));
-    const int nwg = sd_cdiv(tiles, tpw);
+  if (es && Co == 32 && Ci == 4 && Ws == 64 && kh == 5 && kw == 5 && pad == 2 && Hs % 2 == 0 && al16(in)) {
+    // one round of resident workgroups (4 per CU): tpw tiles each. (The round-5 grid was 16 tiles per workgroup: 2048
+    // workgroups at 1024 images, 2.67 rounds of the 768 then resident.)
+    const int tiles = g.M / 128, tpw = sd_cdiv(tiles, 1024), nwg = sd_cdiv(tiles, tpw);
     conv_fwd_direct_pool_c4<32, 6, 5, 4, NW><<<nwg, 256, 0, s>>>(g, G, lhw, tpw, nw, pooled, amax, y, rstd, eps,
                                                                  nchw_flat);
     SD_LAUNCH_CHECK();
@@ -2140,20 +1943,11 @@ extern "C" int sd_conv2d_wgrad(const float* in, const float* dout, float* dw_db,
   g.alpha = 1.f; g.beta = 0.f;
   const bool va = al16(dout) && Co % 4 == 0;
   const bool vb = (Ci % 4 == 0) && al16(in);
-  const int lw = ilog2_exact(G.Wg), lhw = ilog2_exact(G.Hg * G.Wg);
   DirectPlan pl;
   if (va && vb && direct_plan(Nb, Hs, Ws, Ci, Co, kh, kw, ups, pl))
-    return wgrad_direct(in, dout, dw_db, workspace, ws_floats, Nb, Hs, Ws, Ci, Co, kh, kw, pad, J, lw, pl, s, nullptr,
-                        acc);
-  if (conv_algo() == 2 && va && vb && lw >= 0 && lhw >= 0 && (Co == 16 || Co == 32 || Co == 48 || Co == 64)) {
-    const dim3 grid(sd_cdiv(g.N, 128), 1, ks);
-    switch (Co) {
-      case 16: conv_wgrad16<16><<<grid, 256, 0, s>>>(g, G, J, lw, lhw); break;
-      case 32: conv_wgrad16<32><<<grid, 256, 0, s>>>(g, G, J, lw, lhw); break;
-      case 48: conv_wgrad16<48><<<grid, 256, 0, s>>>(g, G, J, lw, lhw); break;
-      default: conv_wgrad16<64><<<grid, 256, 0, s>>>(g, G, J, lw, lhw); break;
-    }
-  } else if (Co <= 32) wgrad_tile<32, 128, 32, 32>(g, G, J, va, vb, s);
+    return wgrad_direct(in, dout, dw_db, workspace, ws_floats, Nb, Hs, Ws, Ci, Co, kh, kw, pad, J, ilog2_exact(G.Wg),
+                        pl, s, nullptr, acc);
+  if (Co <= 32) wgrad_tile<32, 128, 32, 32>(g, G, J, va, vb, s);
   else wgrad_tile<64, 64, 32, 32>(g, G, J, va, vb, s);
   SD_LAUNCH_CHECK();
   if (ks > 1) {
@@ -2177,10 +1971,10 @@ extern "C" int sd_conv2d_wgrad_slabs(int Nb, int Hs, int Ws, int Ci, int Co, int
   return ksplit < 1 ? 1 : ksplit;
 }
 
-// the pooled plan at the largest block (<= wgrad_pool_pix()) whose staging fits
+// the pooled plan at the largest block (<= WGRAD_POOL_PIX) whose staging fits
 static bool pool_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, DirectPlan& pl) {
   if (H % 2 || W % 2) return false;
-  for (int pix = wgrad_pool_pix(); pix >= 128; pix /= 2)
+  for (int pix = WGRAD_POOL_PIX; pix >= 128; pix /= 2)
     if (direct_plan(Nb, H, W, Ci, Co, kh, kw, 0, pl, pix) && pl.ws && pl.nbw == 7 && pl.R % 2 == 0) return true;
   return false;
 }
@@ -2357,21 +2151,9 @@ extern "C" int sd_pool_rms_bwd_compact_film(const float* pooled, const uint8_t* 
 
 // ---------------------------------------------------------------- split-bf16 backward entry points
 namespace {
-}  // namespace
-
-
-namespace {
-// SDHIP_WGRAD3_CI4 (study knob): the split-bf16 direct bwd-weight also for 4-channel inputs (the encoder's first
-// stage, which otherwise stays on the f32 direct kernel) — to measure that stage's gradient parity on split-bf16
-bool wgrad3_ci4() {
-  static int a = -1;
-  if (a < 0) a = getenv("SDHIP_WGRAD3_CI4") ? 1 : 0;
-  return a == 1;
-}
+// (Ci < 16 is refused: the encoder's 4-channel first stage has its own plan, pool3_plan, or the f32 direct kernel)
 bool direct3_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, int ups, DirectPlan& pl) {
-  if (ups != 0 || Co % 4 || Co > 64 || Ci % 4 || Ci < (wgrad3_ci4() ? 4 : 16) || W < 8 || ilog2_exact(W) < 0 ||
-      W > 128)
-    return false;
+  if (ups != 0 || Co % 4 || Co > 64 || Ci % 4 || Ci < 16 || W < 8 || ilog2_exact(W) < 0 || W > 128) return false;
   pl.R = 128 / W < H ? 128 / W : H;
   const int P = pl.R * W;
   if (H % pl.R || P % 32) return false;
@@ -2381,13 +2163,8 @@ bool direct3_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, int ups,
   if (pl.lds > 160 * 1024 || PH * PW * (Ci / 4) > WD_VP * 512 || (Co / 4) * (P / 4) > 512) return false;
   const int J = kh * kw * Ci, JB = (J + 1 + 15) / 16;
   pl.ws = false;
-  // column blocks per wave: the accumulators (TM * NBW * 4 VGPRs) bound it; SDHIP_WGRAD3_NBW overrides (tuning knob)
-  static int nbw_env = -1;
-  if (nbw_env < 0) {
-    const char* e = getenv("SDHIP_WGRAD3_NBW");
-    nbw_env = e ? atoi(e) : 0;
-  }
-  const int nmax = nbw_env > 0 ? nbw_env : (TM <= 3 ? 7 : 4);
+  // column blocks per wave: the accumulators (TM * NBW * 4 VGPRs) bound it
+  const int nmax = TM <= 3 ? 7 : 4;
   pl.gx = (JB + NW_D * nmax - 1) / (NW_D * nmax);
   const int need = (JB + NW_D * pl.gx - 1) / (NW_D * pl.gx);
   pl.nbw = need <= 2 ? 2 : need <= 4 ? 4 : need <= 5 ? 5 : 7;
@@ -2503,82 +2280,55 @@ extern "C" int sd_conv_split3_weight(const float* w, void* wsplit, int rows, int
 }
 
 namespace {
-// SDHIP_CONV6_RING=0: the per-lane-weight kernel (conv_fwd6_direct_pool) instead of the LDS-ring one (A/B knob)
-bool conv6_ring() {  // read per call (host only): tests toggle it in-process
+// SDHIP_CONV6_RING=0: the per-lane-weight kernel (conv_fwd6_direct_pool) instead of the LDS-ring one. Not an A/B
+// switch: the per-lane kernel is the simple form of the algorithm and the bit-exact oracle of the ring kernel's test.
+bool conv6_ring() {  // read per call (host only): the test toggles it in-process
   const char* e = getenv("SDHIP_CONV6_RING");
   return e ? atoi(e) != 0 : true;
 }
-// SDHIP_CONV6_PIPE=1: the ring kernel with the fragment register pipeline, one tile per workgroup (A/B knob; 1 %
-// faster alone than without it, profiles/r06s3b, and slower than the prefetching multi-tile workgroups)
-bool conv6_pipe() {
-  const char* e = getenv("SDHIP_CONV6_PIPE");
-  return e ? atoi(e) != 0 : false;
-}
-template <int BN, int CI, int LW, int KS, bool CG, bool PIPE, int TPW, int MT = 2, int BROW = 40, int NTH = 512,
-          class NW>
+template <int BN, int CI, int LW, int KS, int TPW, int MT, int BROW, class NW>
 int fwd6r_launch_t(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, NW nw, float* pooled,
-                   uint8_t* amax, float* y, float* rstd, float eps, int nchw_flat, size_t lds, hipStream_t s) {
+                   uint8_t* amax, float* y, float* rstd, float eps, int nchw_flat, hipStream_t s) {
+  // the channel-group-major patch (three planes, MT * 128 pixels + halo) and the ring
+  constexpr int W = 1 << LW, R = MT * 128 / W;
+  constexpr size_t lds = (size_t)3 * (R + KS - 1) * (W + KS - 1) * CI * 2 + (size_t)2 * 3 * BN * BROW * 2;
+  static_assert(lds <= 160 * 1024, "LDS");
   static bool raised = false;
   if (!raised) {
-    if (hipFuncSetAttribute(
-            reinterpret_cast<const void*>(conv_fwd6r_direct_pool<BN, CI, LW, KS, CG, PIPE, TPW, MT, BROW, NTH, NW>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd6r_direct_pool<BN, CI, LW, KS, TPW, MT, BROW, NW>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return SD_EARG;
     raised = true;
   }
-  const int nwg = (sd_cdiv(g.M / (16 * MT * (NTH / 64)), TPW) + 7) / 8 * 8;  // a multiple of 8: XCD-contiguous
-  conv_fwd6r_direct_pool<BN, CI, LW, KS, CG, PIPE, TPW, MT, BROW, NTH, NW><<<nwg, NTH, lds, s>>>(
-      g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps, nchw_flat);
+  const int nwg = (sd_cdiv(g.M / (MT * 128), TPW) + 7) / 8 * 8;  // a multiple of 8: XCD-contiguous
+  conv_fwd6r_direct_pool<BN, CI, LW, KS, TPW, MT, BROW, NW><<<nwg, 512, lds, s>>>(g, G, lhw, wsp, nw, pooled, amax, y,
+                                                                                  rstd, eps, nchw_flat);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
-// SDHIP_CONV6_TPW: tiles per workgroup (1, 2, 4, 8, 16); default: enough for one workgroup per CU, at most 16.
-// FiLM stage: on the 32 -> 48 stage's 512-pixel tiles the knob is ignored (always one tile per workgroup: the
-// multi-tile variants there spill); every other shape honours it as the plain stage does.
-// (The fragment pipeline, SDHIP_CONV6_PIPE=1, runs one tile per workgroup: with the prefetched patch it spills.)
-template <int BN, int CI, int LW, int KS, bool CG, class NW>
-int fwd6r_launch(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, NW nw, float* pooled,
-                 uint8_t* amax, float* y, float* rstd, float eps, int nchw_flat, size_t lds, hipStream_t s) {
-  if (conv6_pipe())
-    return fwd6r_launch_t<BN, CI, LW, KS, CG, true, 1>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps, nchw_flat, lds,
-                                                       s);
-  // the 32 -> 48 stage: 512-pixel tiles, 64 pixels per wave, channel-group-major patch, packed ring (356 vs 392 us
-  // alone, profiles/r06mt4), one tile per workgroup by default (its prefetch registers spill: 386 us); SDHIP_CONV6_MT=2:
-  // the 256-pixel tiles
-  if constexpr (CI == 32 && BN == 48) {
-    const char* m = getenv("SDHIP_CONV6_MT");
-    constexpr int R4 = 512 / (1 << LW);
-    constexpr size_t lds4 = (size_t)3 * (R4 + KS - 1) * ((1 << LW) + KS - 1) * CI * 2 + (size_t)2 * 3 * BN * 32 * 2;
-    if ((!m || atoi(m) == 4) && lds4 <= 160 * 1024 && g.M % 512 == 0 && G.Hs % R4 == 0) {
-      const char* e = getenv("SDHIP_CONV6_TPW");
-      const int want = e ? atoi(e) : 1;
-#define SD_F6R4(T) \
-  fwd6r_launch_t<BN, CI, LW, KS, true, false, T, 4, 32>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps, nchw_flat, \
-                                                        lds4, s)
-      // the multi-tile variants of this shape spill (a measurement knob): not instantiated for the FiLM stage
-      if constexpr (is_film<NW>) return SD_F6R4(1);
-      else return want <= 1 ? SD_F6R4(1) : want <= 4 ? SD_F6R4(4) : SD_F6R4(8);
-#undef SD_F6R4
-    }
-  }
-  const char* e = getenv("SDHIP_CONV6_TPW");
-  const int want = e ? atoi(e) : sd_cdiv(g.M / 256, 256);
-#define SD_F6R(T) \
-  fwd6r_launch_t<BN, CI, LW, KS, CG, false, T>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps, nchw_flat, lds, s)
-  return want <= 1 ? SD_F6R(1) : want <= 2 ? SD_F6R(2) : want <= 4 ? SD_F6R(4) : want <= 8 ? SD_F6R(8) : SD_F6R(16);
-#undef SD_F6R
-}
+// The two shapes sd_conv2d_fwd_pool6 accepts (square images: every tile below is whole rows of one image).
+// 32 -> 48 at 32 x 32: 512-pixel tiles, 64 pixels per wave, packed ring (356 vs 392 us alone against the 256-pixel
+// tiles of 32-pixel waves with a padded pixel-major patch, profiles/r06mt4), one tile per workgroup: with more, its
+// prefetch registers spilled (386 us).
+// 48 -> 64 at 16 x 16: whole-image 256-pixel tiles, padded ring, enough tiles per workgroup (1, 2, 4, 8, 16) for one
+// workgroup per CU.
 template <int BN, int CI, int LW, class NW>
 int fwd6_launch(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, NW nw, float* pooled,
                 uint8_t* amax, float* y, float* rstd, float eps, int nchw_flat, hipStream_t s) {
   constexpr int W = 1 << LW, R = 128 / W, KS = 5;
-  constexpr int R2 = 256 / W;
-  // pixel-major patch with its pad where it fits (stage 2), channel-group-major otherwise (stage 3: 165 vs 146 KB)
-  constexpr bool CG = (size_t)3 * (R2 + KS - 1) * (W + KS - 1) * (CI + 8) * 2 + (size_t)2 * 3 * BN * 40 * 2 > 160 * 1024;
-  constexpr size_t lds2 =
-      (size_t)3 * (R2 + KS - 1) * (W + KS - 1) * (CG ? CI : CI + 8) * 2 + (size_t)2 * 3 * BN * 40 * 2;
-  if (conv6_ring() && lds2 <= 160 * 1024 && g.M % 256 == 0 && G.Hs % R2 == 0)
-    return fwd6r_launch<BN, CI, LW, KS, CG>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps, nchw_flat, lds2, s);
+  static_assert((BN == 48 && CI == 32 && LW == 5) || (BN == 64 && CI == 48 && LW == 4), "the two encoder stages");
+  if (conv6_ring()) {
+#define SD_F6R(T, MT, BROW) \
+  fwd6r_launch_t<BN, CI, LW, KS, T, MT, BROW>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps, nchw_flat, s)
+    if constexpr (CI == 32) {
+      return SD_F6R(1, 4, 32);
+    } else {
+      const int want = sd_cdiv(g.M / 256, 256);
+      return want <= 1 ? SD_F6R(1, 2, 40) : want <= 2 ? SD_F6R(2, 2, 40) : want <= 4 ? SD_F6R(4, 2, 40)
+           : want <= 8 ? SD_F6R(8, 2, 40) : SD_F6R(16, 2, 40);
+    }
+#undef SD_F6R
+  }
   const size_t lds = (size_t)3 * (R + KS - 1) * (W + KS - 1) * (CI + 8) * 2;
   static bool raised = false;
   if (!raised && lds > 65536) {
@@ -2642,38 +2392,22 @@ extern "C" int sd_conv_split_weight(const float* w, void* wsplit, int rows, int 
 }
 
 namespace {
-template <int CIN, int NT, int LW>
+// R whole image rows per workgroup as NTHR / 64 waves of 64 pixels, channel-group-major patch
+template <int CIN, int NT, int LW, int R, int NTHR>
 int dgrad_direct_launch(const float* dout, const __bf16* wsp, float* din, int Nb, int H, int pad, hipStream_t s) {
-  constexpr int W = 1 << LW, R = 128 / W, KS = 5;
-  const size_t lds = (size_t)2 * (R + KS - 1) * (W + KS - 1) * (CIN + 8) * 2 + (size_t)2 * 2 * (16 * NT) * 40 * 2;
-  static bool raised = false;
-  if (!raised && lds > 65536) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad3_direct<CIN, NT, LW, KS>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return SD_EARG;
-    raised = true;
-  }
-  conv_dgrad3_direct<CIN, NT, LW, KS><<<Nb * (H / R), 256, lds, s>>>(dout, wsp, din, Nb, H, pad);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
-}
-// 512-pixel tiles over 8 waves of 64 pixels, channel-group-major patch (one workgroup per CU); SDHIP_DGRAD_MT=2: the
-// 128-pixel tiles of 32-pixel waves (two per CU)
-template <int CIN, int NT, int LW>
-int dgrad_direct_launch4(const float* dout, const __bf16* wsp, float* din, int Nb, int H, int pad, hipStream_t s) {
-  constexpr int W = 1 << LW, R = 512 / W, KS = 5;
+  constexpr int W = 1 << LW, KS = 5;
+  static_assert(R * W == NTHR, "64-pixel waves");
   constexpr size_t lds = (size_t)2 * (R + KS - 1) * (W + KS - 1) * CIN * 2 + (size_t)2 * 2 * (16 * NT) * 40 * 2;
   static_assert(lds <= 160 * 1024, "LDS");
-  const char* e = getenv("SDHIP_DGRAD_MT");
-  if ((e && atoi(e) == 2) || H % R) return dgrad_direct_launch<CIN, NT, LW>(dout, wsp, din, Nb, H, pad, s);
+  if (H % R) return SD_ESHAPE;
   static bool raised = false;
   if (!raised) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad3_direct<CIN, NT, LW, KS, 4, true, 512>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad3_direct<CIN, NT, LW, KS, NTHR>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return SD_EARG;
     raised = true;
   }
-  conv_dgrad3_direct<CIN, NT, LW, KS, 4, true, 512><<<Nb * (H / R), 512, lds, s>>>(dout, wsp, din, Nb, H, pad);
+  conv_dgrad3_direct<CIN, NT, LW, KS, NTHR><<<Nb * (H / R), NTHR, lds, s>>>(dout, wsp, din, Nb, H, pad);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
@@ -2685,27 +2419,11 @@ extern "C" int sd_conv2d_dgrad_direct(const float* dout, const void* wsplit, flo
   if (Nb <= 0) return SD_OK;
   if (kh != 5 || kw != 5 || pad != 2 || Hs != Ws || !al16(dout) || !al16(wsplit) || !al16(din)) return SD_ESHAPE;
   const __bf16* wsp = static_cast<const __bf16*>(wsplit);
-  // a workgroup takes 128 / Ws whole rows of one image
-  if (Ci == 48 && Co == 32 && Ws == 32) return dgrad_direct_launch4<48, 2, 5>(dout, wsp, din, Nb, Hs, pad, s);
-  if (Ci == 64 && Co == 48 && Ws == 16) {
-    // whole-image 256-pixel tiles of four 64-pixel waves, channel-group-major patch (183 -> 131 us alone,
-    // profiles/r06dg3); SDHIP_DGRAD3_MT=2: the 128-pixel tiles of 32-pixel waves
-    const char* e = getenv("SDHIP_DGRAD3_MT");
-    if (!(e && atoi(e) == 2) && Hs == 16) {
-      constexpr size_t lds = (size_t)2 * 20 * 20 * 64 * 2 + (size_t)2 * 2 * 48 * 40 * 2;
-      static bool raised = false;
-      if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad3_direct<64, 3, 4, 5, 4, true, 256>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-          return SD_EARG;
-        raised = true;
-      }
-      conv_dgrad3_direct<64, 3, 4, 5, 4, true, 256><<<Nb, 256, lds, s>>>(dout, wsp, din, Nb, Hs, pad);
-      SD_LAUNCH_CHECK();
-      return SD_OK;
-    }
-    return dgrad_direct_launch<64, 3, 4>(dout, wsp, din, Nb, Hs, pad, s);
-  }
+  // 32 x 32 images: 512-pixel tiles (16 rows) over 8 waves, one workgroup per CU
+  if (Ci == 48 && Co == 32 && Ws == 32) return dgrad_direct_launch<48, 2, 5, 16, 512>(dout, wsp, din, Nb, Hs, pad, s);
+  // 16 x 16 images: whole-image 256-pixel tiles over 4 waves (183 -> 131 us alone against 128-pixel tiles of 32-pixel
+  // waves, profiles/r06dg3)
+  if (Ci == 64 && Co == 48 && Ws == 16) return dgrad_direct_launch<64, 3, 4, 16, 256>(dout, wsp, din, Nb, Hs, pad, s);
   return SD_ESHAPE;
 }
 

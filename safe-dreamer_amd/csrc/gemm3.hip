@@ -10,24 +10,10 @@
 namespace {
 using namespace sdb;
 
-#ifndef SD_G3_FP  // fragment-prefetch main loop (gemm3_core.h gemm3_mainloop_fp): measured no faster (4096^3 536 vs 540 us, update 13.85 vs 13.76 ms), off
-#define SD_G3_FP 0
-#endif
-
-// (re-measured on the round-5 tree: 1 / 2 = 10.84 / 10.81 vs 10.80 ms, profiles/r05d2: off)
-#ifndef SD_G3_D2  // two-deep register prefetch main loop (gemm3_core.h gemm3_mainloop_d2): 1 = 128-row tiles, 2 = all
-#define SD_G3_D2 0
-#endif
-template <int BM>
-constexpr bool g3_d2() {
-  return SD_G3_D2 >= 2 || (SD_G3_D2 == 1 && BM >= 128);
-}
-#ifndef SD_G3_M256  // 256 x 128 tiles for the weight-gradient shape (gemm3_run)
-#define SD_G3_M256 0  // measured slower: actor L0 dW 250.7 vs 194.2 us (1 workgroup per CU hides less latency)
-#endif
-#ifndef SD_G3_XCD  // XCD-contiguous tile order (below)
-#define SD_G3_XCD 1
-#endif
+// One main loop (gemm3_core.h gemm3_mainloop). Two others were tried and retired: a fragment-prefetch form measured
+// no faster (4096^3 536 vs 540 us, update 13.85 vs 13.76 ms), and a two-deep register prefetch with a second register
+// set per operand, on the 128-row tiles / on all tiles, measured 10.84 / 10.81 vs 10.80 ms per update (profiles/r05d2).
+//
 // Tile order. The dispatcher deals workgroups to the 8 XCDs round robin by linear id, and each XCD has its own L2:
 // in the plain (x fastest) order the column tiles that share an A row panel run on different XCDs at the same time,
 // so every XCD streams that panel from HBM. Remapped, XCD x runs a contiguous run of the logical order (x fastest,
@@ -38,10 +24,8 @@ constexpr bool g3_d2() {
 SD_DEV void g3_tile(const GemmArgs& g, int& tx, int& ty, int& tz) {
   const int nx = gridDim.x, ny = gridDim.y, nz = gridDim.z;
   int L = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-  if (SD_G3_XCD) {
-    const int T = nx * ny * nz, per = T / 8, rem = T % 8, xcd = L % 8, slot = L / 8;
-    L = xcd * per + (xcd < rem ? xcd : rem) + slot;  // XCD xcd holds per (+1 for the first rem XCDs) tiles
-  }
+  const int T = nx * ny * nz, per = T / 8, rem = T % 8, xcd = L % 8, slot = L / 8;
+  L = xcd * per + (xcd < rem ? xcd : rem) + slot;  // XCD xcd holds per (+1 for the first rem XCDs) tiles
   if (g.sA == 0 && g.batch > 1 && g.ksplit == 1) {  // A broadcast over the batch: x, then batch, then row tile
     tx = L % nx;
     tz = (L / nx) % nz;
@@ -73,15 +57,8 @@ __global__ __launch_bounds__(256, (BM >= 256 ? 1 : 2)) void gemm3_kernel(GemmArg
     f32x4 rsum[OA::NV];
 #pragma unroll
     for (int v = 0; v < OA::NV; ++v) rsum[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (g3_d2<BM>()) {
-      OA la2 = la;
-      OB lb2 = lb;
-      RowSumOp<OA> ra(la, rsum), ra2(la2, rsum);
-      gemm3_mainloop_d2<BM, BN, WM, WN>(ra, lb, ra2, lb2, kbeg, kend, acc);
-    } else {
-      RowSumOp<OA> ra(la, rsum);
-      gemm3_mainloop<BM, BN, WM, WN>(ra, lb, kbeg, kend, acc);
-    }
+    RowSumOp<OA> ra(la, rsum);
+    gemm3_mainloop<BM, BN, WM, WN>(ra, lb, kbeg, kend, acc);
     if (tx == 0) {
       __shared__ float part[(BK / 4) * BM], rows[BM];
       row_sums_km3<BM>(rsum, part, rows);
@@ -96,12 +73,6 @@ __global__ __launch_bounds__(256, (BM >= 256 ? 1 : 2)) void gemm3_kernel(GemmArg
         }
       }
     }
-  } else if (SD_G3_FP) {
-    gemm3_mainloop_fp<BM, BN, WM, WN>(la, lb, kbeg, kend, acc);
-  } else if (g3_d2<BM>()) {
-    OA la2 = la;
-    OB lb2 = lb;
-    gemm3_mainloop_d2<BM, BN, WM, WN>(la, lb, la2, lb2, kbeg, kend, acc);
   } else {
     gemm3_mainloop<BM, BN, WM, WN>(la, lb, kbeg, kend, acc);
   }
@@ -203,16 +174,14 @@ struct KC3Rms {
   }
 };
 
-// BN = 128: 2 x 2 waves of 64 x 64 (2 workgroups per CU). BN = 256 (the heads' 256-column layers): 2 x 2 waves of
-// 64 x 128, one workgroup per CU — each B fragment read from LDS feeds 4 row tiles and each A fragment 8 column tiles,
-// 1.33x the MFMAs per LDS byte of the 64 x 64 wave tile (whose main loop the LDS traffic bounds: MFMA busy ~0.35)
-#ifndef SD_MLP_WIDE  // measured slower on the imagined heads' first layer (335 vs 274 us alone, r04e), neutral on the
-                     // normed hidden layers once that layer moved to gemm3_w256 (update 10.84 vs 10.84 ms, r05mw): off
-#define SD_MLP_WIDE 0
-#endif
-template <bool RMS, bool POUT, int BN>
-__global__ __launch_bounds__(256, BN == 128 ? 2 : 1) void gemm3_mlp_kernel(GemmArgs g, MlpExt e) {
-  constexpr int BM = 128, WM = 64, WN = BN / 2, TM = WM / 16, TN = WN / 16, NP = WN / 64;
+// 128 x 128 tiles: 2 x 2 waves of 64 x 64, 2 workgroups per CU. A 128 x 256 tile for the heads' 256-column layers
+// (2 x 2 waves of 64 x 128, one workgroup per CU, 1.33x the MFMAs per LDS byte of the 64 x 64 wave tile, whose main
+// loop the LDS traffic bounds: MFMA busy ~0.35) was tried and retired: it measured slower on the imagined heads' first
+// layer (335 vs 274 us alone, r04e) and neutral on the normed hidden layers once that layer had moved to
+// gemm3_w256_kernel (update 10.84 vs 10.84 ms, r05mw).
+template <bool RMS, bool POUT>
+__global__ __launch_bounds__(256, 2) void gemm3_mlp_kernel(GemmArgs g, MlpExt e) {
+  constexpr int BM = 128, BN = 128, WM = 64, WN = BN / 2, TM = WM / 16, TN = WN / 16, NP = WN / 64;
   int tx, ty, tz;
   g3_tile(g, tx, ty, tz);
   const int bn0 = tx * BN, bm0 = ty * BM, b = tz;
@@ -237,22 +206,10 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 1) void gemm3_mlp_kernel(GemmA
   if constexpr (RMS) {
     const float* nwb = pick_b(e.nwp, b);
     KC3Rms<BM> la(A, g.lda, g.M, bm0, nwb ? nwb : e.nw + (long)b * e.sNw, rs, e.act);
-    if constexpr (g3_d2<BM>()) {
-      KC3Rms<BM> la2 = la;
-      KC3<BN, true> lb2 = lb;
-      gemm3_mainloop_d2<BM, BN, WM, WN>(la, lb, la2, lb2, 0, g.K, acc);
-    } else {
-      gemm3_mainloop<BM, BN, WM, WN>(la, lb, 0, g.K, acc);
-    }
+    gemm3_mainloop<BM, BN, WM, WN>(la, lb, 0, g.K, acc);
   } else {
     KC3<BM, true> la(A, g.lda, g.M, bm0);
-    if constexpr (g3_d2<BM>()) {
-      KC3<BM, true> la2 = la;
-      KC3<BN, true> lb2 = lb;
-      gemm3_mainloop_d2<BM, BN, WM, WN>(la, lb, la2, lb2, 0, g.K, acc);
-    } else {
-      gemm3_mainloop<BM, BN, WM, WN>(la, lb, 0, g.K, acc);
-    }
+    gemm3_mainloop<BM, BN, WM, WN>(la, lb, 0, g.K, acc);
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave / (BN / WN), wc = wave % (BN / WN), l16 = lane & 15, q = lane >> 4;
@@ -300,7 +257,7 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 1) void gemm3_mlp_kernel(GemmA
   }
 }
 
-// ---- The wide form for long layers without an input norm (SD_MLP_W256; the imagined heads' first layers: M = H1 * N
+// ---- The wide form for long layers without an input norm (the imagined heads' first layers: M = H1 * N
 // = 16,384 rows, K = feat 2,560, four 256-wide heads on one input). One 256 x 256 tile per workgroup = one entry's
 // whole width over 256 rows: 512 threads as 2 (rows) x 4 (columns) waves of 128 x 64, on v_mfma_f32_32x32x16_bf16
 // (twice the FLOP per fragment byte of the 16x16x32 tile, so the LDS reads stay under half the MFMA time). Against
@@ -310,12 +267,6 @@ __global__ __launch_bounds__(256, BN == 128 ? 2 : 1) void gemm3_mlp_kernel(GemmA
 // the other LDS stage after them, one barrier per k tile. Same split products as gemm3_core.h (lo*hi, hi*lo, hi*hi per
 // 16-deep step); the 32x32 MFMA sums its 16 k in its own order, so the results differ from the 128 x 128 kernel's at
 // the split's ~1e-5 level, not bit for bit.
-#ifndef SD_MLP_W256
-#define SD_MLP_W256 1
-#endif
-#ifndef SD_W256_PASSES
-#define SD_W256_PASSES 1
-#endif
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 namespace w256 {
 constexpr int BM = 256, BN = 256, NT = 512, WM = 128, WN = 64, TM = WM / 32, TN = WN / 32;
@@ -396,7 +347,7 @@ __global__ __launch_bounds__(512, 1) void gemm3_w256_kernel(GemmArgs g, MlpExt e
         ah[i] = *reinterpret_cast<const bf16x8*>(p);
         al[i] = *reinterpret_cast<const bf16x8*>(p + BK);
       }
-#if SD_W256_PASSES  // the three products as three passes over the 8 accumulators (no dependent MFMA back to back)
+      // the three products as three passes over the 8 accumulators (no dependent MFMA back to back)
 #pragma unroll
       for (int u = 0; u < 3 * TM * TN; ++u) {
         const int pass = u / (TM * TN), i = (u / TN) % TM, j = u % TN;
@@ -405,18 +356,6 @@ __global__ __launch_bounds__(512, 1) void gemm3_w256_kernel(GemmArgs g, MlpExt e
                                                            acc[i][j], 0, 0, 0);
         if (u % 6 == 5) store1(y, nxt, u / 6, s);
       }
-#else
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-        store1(y, nxt, i, s);
-      }
-#endif
     }
     __syncthreads();
   };
@@ -511,7 +450,7 @@ extern "C" int sd_gemm_bf16x3_mlp(const sd_gemm_desc* d, const sd_mlp_ext* x, sd
   hipStream_t st = (hipStream_t)stream_;
   // long layers without an input norm, one 256-wide entry per tile: the 256 x 256 kernel once it fills the chip
   // (SDHIP_MLP_NOW256 set: the 128-tile kernel instead, for the agreement test of the two paths)
-  if (SD_MLP_W256 && !rms && g.N == 256 && (long)sd_cdiv(g.M, 256) * g.batch >= 192 && !getenv("SDHIP_MLP_NOW256")) {
+  if (!rms && g.N == 256 && (long)sd_cdiv(g.M, 256) * g.batch >= 192 && !getenv("SDHIP_MLP_NOW256")) {
     const dim3 grid(sd_cdiv(g.M, 256) * g.batch);
     // (no LDS pad: its 147 KB already hold the CU)
     if (pout) hipLaunchKernelGGL((gemm3_w256_kernel<true>), grid, dim3(512), 0, st, g, e);
@@ -519,19 +458,11 @@ extern "C" int sd_gemm_bf16x3_mlp(const sd_gemm_desc* d, const sd_mlp_ext* x, sd
     SD_LAUNCH_CHECK();
     return SD_OK;
   }
-  // 256-column tiles where the layer is exactly that wide (every imagined head's hidden layers), else 128
-  const bool wide = SD_MLP_WIDE && g.N % 256 == 0;
-#define SD_MLP_LAUNCH(BN_)                                                                             \
-  do {                                                                                                 \
-    const dim3 grid(sd_cdiv(g.N, BN_), sd_cdiv(g.M, 128), g.batch);                                    \
-    if (rms && pout) gemm3_mlp_kernel<true, true, BN_><<<grid, 256, 0, st>>>(g, e);                    \
-    else if (rms) gemm3_mlp_kernel<true, false, BN_><<<grid, 256, 0, st>>>(g, e);                      \
-    else if (pout) gemm3_mlp_kernel<false, true, BN_><<<grid, 256, 0, st>>>(g, e);                     \
-    else gemm3_mlp_kernel<false, false, BN_><<<grid, 256, 0, st>>>(g, e);                              \
-  } while (0)
-  if (wide) SD_MLP_LAUNCH(256);
-  else SD_MLP_LAUNCH(128);
-#undef SD_MLP_LAUNCH
+  const dim3 grid(sd_cdiv(g.N, 128), sd_cdiv(g.M, 128), g.batch);
+  if (rms && pout) gemm3_mlp_kernel<true, true><<<grid, 256, 0, st>>>(g, e);
+  else if (rms) gemm3_mlp_kernel<true, false><<<grid, 256, 0, st>>>(g, e);
+  else if (pout) gemm3_mlp_kernel<false, true><<<grid, 256, 0, st>>>(g, e);
+  else gemm3_mlp_kernel<false, false><<<grid, 256, 0, st>>>(g, e);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
@@ -566,9 +497,10 @@ extern "C" int sd_gemm_bf16x3_wgrad2(const sd_gemm_desc* d, float* workspace, lo
 }
 
 namespace {
-#ifndef SD_G3_T128  // 128 x 128 tiles once the launch has this many of them (else 64 x 64). 192 (was 256): the S2
-#define SD_G3_T128 192  // input-gradient GEMMs of the imagined actor / value (240 tiles of 128) on 128 x 128 tiles, one
-#endif              // round of workgroups: update 10.86 -> 10.79 ms over 6 same-box rounds, bit-identical (r05t128*)
+// 128 x 128 tiles once the launch has this many of them (else 64 x 64). 192 (was 256): the S2 input-gradient GEMMs
+// of the imagined actor / value (240 tiles of 128) on 128 x 128 tiles, one round of workgroups: update 10.86 ->
+// 10.79 ms over 6 same-box rounds, bit-identical (r05t128*)
+constexpr long G3_T128 = 192;
 int gemm3_run(const sd_gemm_desc* d, float* workspace, long workspace_floats, float* rowsum, int rs_acc,
               sd_stream stream_, int rs_split, float* rowsum2) {
   hipStream_t stream = (hipStream_t)stream_;
@@ -596,10 +528,10 @@ int gemm3_run(const sd_gemm_desc* d, float* workspace, long workspace_floats, fl
   const bool ak = d->a_kcontig != 0, bk = d->b_kcontig != 0;
   if (tile != 0 && tile != 1 && tile != 2) {
     const long tiles128 = (long)sd_cdiv(d->M, 128) * sd_cdiv(d->N, 128) * d->batch * ks;
-    tile = tiles128 >= SD_G3_T128 ? 0 : 1;
-    // weight-gradient shape (M <= 256 output rows, long split K, both operands rows-contiguous: dW = dy^T x): one
-    // 256-row tile covers every M, so each k chunk of x is read once instead of once per 128-row tile
-    if (SD_G3_M256 && !ak && !bk && d->M > 128 && d->M <= 256 && ks > 1 && g.kchunk >= 512 && tile == 0) tile = 2;
+    // (256 x 128 tiles for the weight-gradient shape, M <= 256 output rows and a long split K, so that each k chunk of
+    // x is read once: measured slower, actor L0 dW 250.7 vs 194.2 us, 1 workgroup per CU hides less latency. Retired
+    // as an automatic choice; tile = 2 still asks for them.)
+    tile = tiles128 >= G3_T128 ? 0 : 1;
   }
   if (tile == 2 && (ak || bk)) tile = 0;
   if (ak && bk) launch3_layout<true, true>(g, tile, va, vb, stream);

@@ -580,7 +580,7 @@ def conv2d_dgrad(dout, w, pad=None, fast=True, direct=True):
     if fast and FAST_GEMM:
         Nb, H, W, _ = dout.shape
         din = torch.empty(Nb, H, W, Ci, dtype=torch.float32, device=dout.device)
-        if direct and DIRECT_DGRAD:  # the dOut patch staged once per workgroup (same products and order per k)
+        if direct:  # the dOut patch staged once per workgroup (same products and order per k)
             ws = _SPLIT.get(w.data_ptr())
             if ws is None:
                 ws = conv_split_weight(wf)
@@ -679,17 +679,14 @@ def conv2d_wgrad_pool(x, dpool, amax, kh, kw, pad=None, acc=None):
 _FLIP = {}  # weight data_ptr -> flipped weight, built ahead of the backward (set_flip_cache)
 _SPLIT = {}  # weight data_ptr -> split-bf16 image of the flipped weight (sd_conv_split_weight), same lifetime
 # SDREAMER_CONV6: the encoder stages' forward on the fp32-accurate three-way split-bf16 direct kernel
-# (sd_conv2d_fwd_pool6, the weight through an LDS ring) instead of the exact f32 kernels. Default "1": every
+# (sd_conv2d_fwd_pool6, the weight through an LDS ring) instead of the exact f32 kernels. Default on: every
 # instantiated stage — 32 -> 48 channels at 32 x 32 (0.67 -> 0.40 ms) and 48 -> 64 at 16 x 16 (0.38 -> 0.19 ms,
-# profiles/r06s3b); "s2" the first of them only, "0" none. Round 6 measured its parity against exact arithmetic
+# profiles/r06s3b); 0 = none. Round 6 measured its parity against exact arithmetic
 # (tools/precision_study.py over the golden cases' LaProp moments, profiles/r06f, r06s3b): it sits as close to the
 # float64 answer as the f32 kernels do in every golden case, and closer where the reference's own f32 is far from it
 # (walker_r2_nowarm's first conv layer: 0.02 of the bound from float64, the reference 5.1; the golden update test
 # accepts the reference's answer or exact arithmetic per tensor there).
-CONV6 = os.environ.get("SDREAMER_CONV6", "1")
-CONV6 = CONV6 if CONV6 in ("1", "s2") else ""
-# SDREAMER_DIRECT_DGRAD=0: the encoder's bwd-data on the implicit-GEMM split-bf16 kernel (A/B knob)
-DIRECT_DGRAD = os.environ.get("SDREAMER_DIRECT_DGRAD", "1") != "0"
+CONV6 = os.environ.get("SDREAMER_CONV6", "1") == "1"
 
 
 def set_flip_cache(weights):
@@ -700,7 +697,7 @@ def set_flip_cache(weights):
     _SPLIT.clear()
     for w in weights:
         _FLIP[w.data_ptr()] = conv_flip_weight(w)
-        if FAST_GEMM and DIRECT_DGRAD:
+        if FAST_GEMM:
             _SPLIT[w.data_ptr()] = conv_split_weight(_FLIP[w.data_ptr()])
     return list(_FLIP.values()) + list(_SPLIT.values())
 
@@ -792,7 +789,7 @@ def conv2d_fwd_pool(x, w, b, nw, nchw_flat=False, film=None):
     if film is not None:
         gamma, beta, ipc = _film_args(film, Nb, Co)
         sfx, fa = "_film", (p(gamma), p(beta), ipc)
-    if CONV6 and (CONV6 == "1" or (Ci, Co) == (32, 48)):  # fp32-accurate three-way split-bf16 direct kernel
+    if CONV6:  # fp32-accurate three-way split-bf16 direct kernel
         K = kh * kw * Ci
         ws = torch.empty(3 * Co * (-(-K // 32) * 32), dtype=torch.int16, device=x.device)
         nat.call("sd_conv_split3_weight", p(_c(w)), p(ws), Co, K, stream())

@@ -321,29 +321,22 @@ def test_conv_pool_fused_matches_two_launches(ci, co, hw, nb, nchw, monkeypatch)
             close(a.nan_to_num(), r.nan_to_num(), 1e-6, what)
 
 
-@pytest.mark.parametrize("nb", [3, 40])
+@pytest.mark.parametrize("nb", [3, 40, 65])
 def test_conv_pool_c4_grid_bit_identical(nb, monkeypatch):
     """Stage-1 direct kernel (conv_fwd_direct_pool_c4): every tile runs the same products in the same order whatever
-    the grid, so the default one-round grid (SDHIP_C4_OCC resident workgroups per CU, 32 tiles each at the bench's
-    1024 images), the round-5 grid (SDHIP_C4_TPW=16), a ragged 3 tiles per workgroup and a 3-per-CU round all give
-    bit-identical outputs; nb = 3 leaves most workgroups of the default grid without a tile."""
+    the grid. The default grid is one round of resident workgroups, cdiv(tiles, 1024) tiles each (32 tiles per image):
+    nb = 3, 40, 65 give 1, 2 and 3 tiles per workgroup, the last ragged (2080 tiles over 694 workgroups). Each must be
+    bit-identical to the same images run in chunks of at most 32 images (one tile per workgroup) and concatenated."""
     from sdreamer import kernels as K
     monkeypatch.setattr(K, "CONV6", "")
     x = (torch.rand(nb, 64, 64, 4, generator=_g(nb)) - 0.5).to(DEV)
     w = (torch.randn(32, 5, 5, 4, generator=_g(7)) / 10).to(DEV)
     b = (0.1 * torch.randn(32, generator=_g(1))).to(DEV)
     nw = (1 + 0.1 * torch.randn(32, generator=_g(2))).to(DEV)
-    monkeypatch.delenv("SDHIP_C4_TPW", raising=False)
-    monkeypatch.delenv("SDHIP_C4_OCC", raising=False)
-    ref = [t.clone() for t in K.conv2d_fwd_pool(x, w, b, nw)]
-    for env in ({"SDHIP_C4_TPW": "16"}, {"SDHIP_C4_TPW": "3"}, {"SDHIP_C4_TPW": "1"}, {"SDHIP_C4_OCC": "3"}):
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        out = K.conv2d_fwd_pool(x, w, b, nw)
-        for a, r, what in zip(out, ref, ("y", "pooled", "amax", "rstd")):
-            assert torch.equal(a, r), (env, what)
-        for k in env:
-            monkeypatch.delenv(k)
+    out = K.conv2d_fwd_pool(x, w, b, nw)
+    chunks = [K.conv2d_fwd_pool(x[i:i + 32], w, b, nw) for i in range(0, nb, 32)]
+    for k, what in enumerate(("y", "pooled", "amax", "rstd")):
+        assert torch.equal(out[k], torch.cat([c[k] for c in chunks])), what
 
 
 def test_upconv():
@@ -712,46 +705,44 @@ def test_conv_pool_bf16x6_matches_f32(ci, co, hw, nb, nchw, monkeypatch):
     close(y6.nan_to_num(), yr.nan_to_num(), 1e-5, "y")
 
 
-@pytest.mark.parametrize("ci,co,hw,nb,nchw", [(32, 48, 32, 4, False), (32, 48, 32, 3, True), (48, 64, 16, 5, True),
-                                               (48, 64, 16, 2, False)])
-def test_conv_pool_bf16x6_ring_bit_identical(ci, co, hw, nb, nchw, monkeypatch):
-    """The bf16x6 stage forward with the weight through the LDS ring (conv_fwd6r_direct_pool: the 32 -> 48 stage on
-    512-pixel tiles with 64 pixels per wave, or 256 / 32 (SDHIP_CONV6_MT=2); the 48 -> 64 stage on 256-pixel tiles and
-    the channel-group-major patch) against the per-lane-weight kernel (SDHIP_CONV6_RING=0, 128-pixel tiles), one tile or
-    several per workgroup, with or without the fragment pipeline: the same products in the same k order, so every
-    output is bit-identical."""
+@pytest.mark.parametrize("ci,co,hw,nb,nchw,film", [
+    pytest.param(32, 48, 32, 4, False, 0, id="32-48-32-4-False"),
+    pytest.param(32, 48, 32, 3, True, 0, id="32-48-32-3-True"),
+    pytest.param(48, 64, 16, 5, True, 0, id="48-64-16-5-True"),
+    pytest.param(48, 64, 16, 2, False, 0, id="48-64-16-2-False"),
+    (48, 64, 16, 257, False, 0), (48, 64, 16, 513, True, 0), (48, 64, 16, 1025, False, 0),
+    (48, 64, 16, 2049, True, 0),
+    (48, 64, 16, 5, False, 1), (48, 64, 16, 5, True, 5), (48, 64, 16, 513, True, 1), (48, 64, 16, 513, False, 513)])
+def test_conv_pool_bf16x6_ring_bit_identical(ci, co, hw, nb, nchw, film, monkeypatch):
+    """The bf16x6 stage forward with the weight through the LDS ring (conv_fwd6r_direct_pool) against the
+    per-lane-weight kernel (SDHIP_CONV6_RING=0, 128-pixel tiles): the same products in the same k order, so every
+    output is bit-identical. The shapes drive the ring kernel's variants. 32 -> 48 at 32 x 32: 512-pixel tiles with 64
+    pixels per wave, one per workgroup; nb = 3 is 6 tiles on a grid rounded up to 8 (idle workgroups). 48 -> 64 at
+    16 x 16: one 256-pixel tile per image, cdiv(nb, 256) -> 1, 2, 4, 8, 16 tiles per workgroup: nb = 2, 5 one; 257,
+    513, 1025, 2049 two to sixteen, each 129 workgroups rounded to 136 (a ragged last range and idle workgroups).
+    film > 0: the FiLM stage (gamma, beta with that many context rows) on the same kernels."""
     from sdreamer import kernels as K
     x = (torch.rand(nb, hw, hw, ci, generator=_g(21)) - 0.5).to(DEV)
     w = (torch.randn(co, 5, 5, ci, generator=_g(22)) / (ci * 25) ** 0.5).to(DEV)
     b = (0.1 * torch.randn(co, generator=_g(23))).to(DEV)
     nw = (1 + 0.1 * torch.randn(co, generator=_g(24))).to(DEV)
+    fm = None
+    if film:
+        fm = ((1 + 0.5 * torch.randn(film, co, generator=_g(25))).to(DEV),
+              (0.5 * torch.randn(film, co, generator=_g(26))).to(DEV))
     monkeypatch.setattr(K, "CONV6", "1")
-    rings = [K.conv2d_fwd_pool(x, w, b, nw, nchw_flat=nchw)]
-    for tpw in ("3", "16"):  # multi-tile workgroups (the bench's default), ragged tile ranges, idle workgroups
-        monkeypatch.setenv("SDHIP_CONV6_TPW", tpw)
-        rings.append(K.conv2d_fwd_pool(x, w, b, nw, nchw_flat=nchw))
-    monkeypatch.setenv("SDHIP_CONV6_MT", "2")  # (32 -> 48: 256-pixel tiles, 32 pixels per wave; default 4: 512, 64)
-    for tpw in ("1", "3"):
-        monkeypatch.setenv("SDHIP_CONV6_TPW", tpw)
-        rings.append(K.conv2d_fwd_pool(x, w, b, nw, nchw_flat=nchw))
-    monkeypatch.delenv("SDHIP_CONV6_MT")
-    monkeypatch.delenv("SDHIP_CONV6_TPW")
-    monkeypatch.setenv("SDHIP_CONV6_PIPE", "1")
-    rings.append(K.conv2d_fwd_pool(x, w, b, nw, nchw_flat=nchw))
-    monkeypatch.delenv("SDHIP_CONV6_PIPE")
+    ring = K.conv2d_fwd_pool(x, w, b, nw, nchw_flat=nchw, film=fm)
     monkeypatch.setenv("SDHIP_CONV6_RING", "0")
-    lane = K.conv2d_fwd_pool(x, w, b, nw, nchw_flat=nchw)
-    for ring in rings:
-        for a, r, what in zip(ring, lane, ("y", "pooled", "amax", "rstd")):
-            assert torch.equal(a, r), what
+    lane = K.conv2d_fwd_pool(x, w, b, nw, nchw_flat=nchw, film=fm)
+    for a, r, what in zip(ring, lane, ("y", "pooled", "amax", "rstd")):
+        assert torch.equal(a, r), what
 
 
 @pytest.mark.parametrize("cd,ci,hw,nb", [(48, 32, 32, 8), (64, 48, 16, 16), (48, 32, 32, 1)])
-def test_conv_dgrad_direct_matches_implicit_gemm(cd, ci, hw, nb, monkeypatch):
+def test_conv_dgrad_direct_matches_implicit_gemm(cd, ci, hw, nb):
     """The direct bwd-data kernel (sd_conv2d_dgrad_direct: dOut patch staged once per workgroup; the 48 -> 32 stage on
-    512-pixel tiles of 64-pixel waves and the 64 -> 48 one on whole-image tiles of 64-pixel waves, or both on 128-pixel
-    tiles of 32-pixel waves with SDHIP_DGRAD_MT=2 / SDHIP_DGRAD3_MT=2) against the implicit-GEMM one
-    (sd_conv2d_dgrad_bf16x3): the same (hi, lo) splits, the same three products per k and the same k order, so bit for
+    512-pixel tiles of 64-pixel waves and the 64 -> 48 one on whole-image tiles of 64-pixel waves) against the
+    implicit-GEMM one (sd_conv2d_dgrad_bf16x3): the same (hi, lo) splits, the same three products per k and the same k order, so bit for
     bit the same dIn; and both within the split-bf16 bound of the f32 kernel."""
     from sdreamer import kernels as K
     w = (torch.randn(cd, 5, 5, ci, generator=_g(cd + ci)) / (ci * 25) ** 0.5).to(DEV)
@@ -763,13 +754,6 @@ def test_conv_dgrad_direct_matches_implicit_gemm(cd, ci, hw, nb, monkeypatch):
                              K.stream()), "direct kernel not instantiated for this shape"
     dx_gemm = K.conv2d_dgrad(dy, w, fast=True, direct=False)
     assert torch.equal(dx, dx_gemm)
-    for knob, val in (("SDHIP_DGRAD_MT", "2"), ("SDHIP_DGRAD3_MT", "2")):  # (each applies to one stage)
-        monkeypatch.setenv(knob, val)
-        dx2 = torch.empty_like(dx)
-        assert K.nat.call_shaped("sd_conv2d_dgrad_direct", K.p(dy), K.p(ws), K.p(dx2), nb, hw, hw, cd, ci, 5, 5, 2,
-                                 K.stream())
-        monkeypatch.delenv(knob)
-        assert torch.equal(dx2, dx_gemm), knob
     dx_ref = K.conv2d_dgrad(dy, w, fast=False)
     bound = 4e-5 * K.conv2d_dgrad(dy.abs(), w.abs(), fast=False) + 1e-6
     assert ((dx - dx_ref).abs() - bound).max().item() <= 0

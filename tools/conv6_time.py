@@ -1,7 +1,6 @@
-"""Encoder stage forward, per kernel variant, at the bench's B*L = 1024 images (GPU box, measurement aid):
-exact f32 (sd_conv2d_fwd_pool), bf16x6 per-lane weight (SDHIP_CONV6_RING=0) and bf16x6 LDS ring, for the 32 -> 48
-stage at 32 x 32 and the 48 -> 64 stage at 16 x 16; the ring kernel one tile per workgroup (with / without the
-fragment pipeline) and with its default multi-tile workgroups (SDHIP_CONV6_TPW). Prints median us of back-to-back launches.
+"""Encoder stage forward, per kernel, at the bench's B*L = 1024 images (GPU box, measurement aid): exact f32
+(sd_conv2d_fwd_pool), bf16x6 per-lane weight (SDHIP_CONV6_RING=0, the ring kernel's test oracle) and bf16x6 LDS ring,
+for the 32 -> 48 stage at 32 x 32 and the 48 -> 64 stage at 16 x 16. Prints median us of back-to-back launches.
   python tools/conv6_time.py"""
 import os
 import sys
@@ -36,23 +35,9 @@ def main():
         b = torch.zeros(co).cuda()
         nw = torch.ones(co).cuda()
         res = {}
-        for name, c6, ring, pipe, tpw in [("f32", "", "1", "0", ""), ("bf16x6 lane", "1", "0", "0", ""),
-                                          ("bf16x6 ring pipe 1 tile", "1", "1", "1", ""),
-                                          ("bf16x6 ring MT2 1 tile", "1", "1", "0", "mt2:1"),
-                                          ("bf16x6 ring MT2", "1", "1", "0", "mt2:"),
-                                          ("bf16x6 ring MT4 prefetch x4", "1", "1", "0", "mt4:4"),
-                                          ("bf16x6 ring", "1", "1", "0", "")]:
+        for name, c6, ring in [("f32", False, "1"), ("bf16x6 lane", True, "0"), ("bf16x6 ring", True, "1")]:
             K.CONV6 = c6
             os.environ["SDHIP_CONV6_RING"] = ring
-            os.environ["SDHIP_CONV6_PIPE"] = pipe
-            os.environ.pop("SDHIP_CONV6_MT", None)
-            if tpw.startswith("mt"):  # the 32 -> 48 stage's m tiles per wave (the 48 -> 64 stage has 2 either way)
-                os.environ["SDHIP_CONV6_MT"] = tpw[2]
-                tpw = tpw[4:]
-            if tpw:
-                os.environ["SDHIP_CONV6_TPW"] = tpw
-            else:
-                os.environ.pop("SDHIP_CONV6_TPW", None)
             res[name] = timeit(lambda: K.conv2d_fwd_pool(x, w, b, nw))
         flop = 2 * 1024 * hw * hw * co * 25 * ci
         print(f"stage {ci}->{co} at {hw}x{hw}: " + "  ".join(f"{k} {v:.1f} us" for k, v in res.items()) +

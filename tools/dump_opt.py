@@ -1,5 +1,5 @@
-"""GPU box: the golden cases' two product updates with the current environment (e.g. SDREAMER_CONV6=s2, the encoder's
-second stage forward on bf16x6), their sampled LaProp moments dumped as tools/grad_attrib.py reads them — no
+"""GPU box: the golden cases' two product updates with the current environment (e.g. SDREAMER_CONV6=0, the encoder's
+forward on the exact f32 kernels), their sampled LaProp moments dumped as tools/grad_attrib.py reads them — no
 assertions, so a variant that leaves a golden bound can still be compared against float64.
   python tools/dump_opt.py <out dir> [case ...]"""
 import os

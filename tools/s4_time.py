@@ -9,7 +9,7 @@ sys.path.insert(0, os.path.join(ROOT, "safe-dreamer_amd"))
 import torch  # noqa: E402
 
 from sdreamer import kernels as K  # noqa: E402
-from c4_time import timeit  # noqa: E402
+from conv6_time import timeit  # noqa: E402
 
 
 def main():
