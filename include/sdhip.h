@@ -490,17 +490,19 @@ int sd_barlow_dist_dx(const float* x1, const float* dn1, const float* sums, cons
                       const float* A, float Nt, float world, long R, int E, float* dx1, sd_stream stream);
 
 /* ---------------------------------------------------------------- fused RSSM posterior scan (ObserveScan)
- * RSSM.observe's recurrence (rssm.py:140-178 + Deter.forward rssm.py:36-75) for B <= 16 rows per step, as
- * 5 fused launches per step forward and 6 per step backward (instead of ~15 / ~20 separate kernels): every launch is
+ * RSSM.observe's recurrence (rssm.py:140-178 + Deter.forward rssm.py:36-75) for B <= 4096 rows per step (row tiles of
+ * <= 16 rows side by side in each launch), as 4 fused launches per step forward (5 at step 0) and 5 per step backward
+ * (instead of ~15 / ~20 separate kernels): every launch but the logits-by-rows one is
  * an M=16 MFMA contraction whose A panel is built in LDS by a fused prologue (split-K slab reduction, RMSNorm+SiLU,
  * straight-through sampler backward, RMSNorm backward) and whose epilogue fuses bias, the GRU gate fwd/bwd, the
  * unimix sampler and the reset masks. Recurrence-free work (action branch, embed half of obs_net_0, all weight
  * gradients) stays outside as (T*B)-row GEMMs. Weight operands are k-contiguous (row n of a [N][K] matrix);
  * the backward uses transposed copies the caller prepares once per update. Time-major (T,B,.) activations.
- * Requirements: B <= 16; D % G == 0; U, D/G, S*Kd multiples of 64; Kd in {16, 32, 64}. */
+ * Requirements: B <= 4096; G <= 8; U == 256; D/G in {256, 512}; D <= 4096; S*Kd in {512, 1024}; Kd in {16, 32, 64}. */
 typedef struct sd_rssm_scan {
   int B, T, D, U, SK, Kd, G;
-  int ks_d, ks_s;              /* K splits of the D-wide and SK-wide step GEMMs (slabs summed by the consumer) */
+  int ks_d, ks_s;              /* ks_d: K splits of the D-wide step GEMMs (1..8, D % (16 ks_d) == 0; slabs summed by
+                                  the consumer). ks_s: reserved, not read (the SK-wide product is always 8 slabs) */
   float eps, unimix;
   uint64_t seed;
   const uint64_t* seed_ptr;    /* optional device seed offset (graph replay) */
@@ -554,9 +556,9 @@ int sd_rssm_scan_work_floats(const sd_rssm_scan* d);
 int sd_rssm_scan_fwd(const sd_rssm_scan* d, sd_stream stream);
 int sd_rssm_scan_bwd(const sd_rssm_scan* d, sd_stream stream);
 /* Measurement aid (bench.py): one launch of forward step t's phase `which` as sd_rssm_scan_fwd issues it, after a run
- * on the same descriptor: 0 = x1p slab (k_slab), 1 = _dyn_hid (k_hid), 2 = _dyn_gru + GRU (k_gate), 3 = obs_net_0 deter
- * half + next _dyn_in0 (k_slab), 4 = obs_net logits + sampler (k_logit). Only t = T - 1 rewrites the values the run
- * wrote. */
+ * on the same descriptor: 0 = x1p slab (k_slab; a run issues it at step 0 only), 1 = _dyn_hid (k_hid), 2 = _dyn_gru +
+ * GRU (k_gate), 3 = obs_net_0 deter half + next _dyn_in0 (k_slab), 4 = obs_net logits + sampler + the next step's x1p
+ * slabs (k_logit_rows). Only t = T - 1 rewrites the values the run wrote. */
 int sd_rssm_scan_step_kernel(const sd_rssm_scan* d, int which, int t, sd_stream stream);
 
 /* ---------------------------------------------------------------- fused imagination (Dreamer._imagine)

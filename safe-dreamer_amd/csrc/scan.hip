@@ -5,11 +5,15 @@
 // Why launches and not one persistent kernel: on MI355X a dependent kernel boundary costs ~1.5 us, an XCD-
 // hierarchical grid barrier ~4-5 us (MI355X_MICROARCH.md price list), so the win is in FEWER, FATTER launches:
 // the ~15 kernels of a forward step (mask, GEMM, norm, GEMM, norm, GEMM, block GEMM, norm, block GEMM, GRU, GEMM,
-// norm, GEMM, sampler) become 5, the ~20 of a backward step become 6. Every launch is an M=16 MFMA contraction
-// (v_mfma_f32_16x16x4_f32, exact fp32) over weights streamed once from L2/MALL:
-//   * 512-thread workgroups, one 16-column output tile (or 3 / Kd/16 tiles) each; the 8 waves take interleaved
-//     16-deep k chunks, all of a wave's weight float4s are issued BEFORE the prologue runs, so the weight stream
-//     overlaps the prologue's own loads;
+// norm, GEMM, sampler) become 4 (k_hid, k_gate, k_slab, k_logit_rows; step 0 has a fifth, the x1p k_slab), the ~20 of
+// a backward step become 5 (k_dlogit, k_dgru, k_dhh, k_dhp, k_carry). The file builds one way: each schedule choice
+// (chunk pairing, XCD-contiguous tiles, 8 x1p slabs, k_gate's 8-column workgroups, one d_xcat slab per block, logits
+// by rows) was a build-time switch once and is fixed at the value that won its measurement; only
+// the -DSD_SCAN_TRACE measurement build remains. Every launch but k_logit_rows (fp32 dot products by rows) is an M=16
+// MFMA contraction (v_mfma_f32_16x16x4_f32, exact fp32) over weights streamed once from L2/MALL:
+//   * 512-thread workgroups, one 16-column output tile each (k_gate: 8 deter columns as two tiles; k_carry: Kd/16
+//     tiles); the 8 waves take interleaved 16-deep k chunks, all of a wave's weight float4s are issued BEFORE the
+//     prologue runs, so the weight stream overlaps the prologue's own loads;
 //   * the A panel (16 rows x K) is built in LDS by a fused prologue: split-K slab reduction + bias + RMSNorm + SiLU,
 //     the straight-through sampler's backward (noise recomputed from the counter-based Philox stream), or an
 //     RMSNorm backward; row stride K+4 floats keeps the ds_read_b128 fragment loads conflict-free;
@@ -39,18 +43,13 @@ SD_DEV float dsilu(float z) {
 // ------------------------------------------------------------------------------------------- contraction core
 // acc[t] += A[0:16, span] . W_t[n_t + 0:16, span]^T.  Wave w owns 16-deep k chunks; lane group q = lane>>4 supplies
 // k = 16c + 4q .. +3 as one float4 and the MFMA consumes them in 4 steps (a permuted but consistent k order).
-// SD_CORE_PAIR: a wave's chunks come in adjacent pairs (2w, 2w + 1, 2w + 16, 2w + 17, ...), so the two loads it issues
-// back to back for a row cover one whole 128-B line (with single chunks c = w, w + 8, ... each 128-B line of a weight
-// row was split between two waves' loads, issued at different times).
-#ifndef SD_CORE_PAIR
-#define SD_CORE_PAIR 1
-#endif
-SD_DEV int core_chunk(int wave, int c) {
-  return SD_CORE_PAIR ? 2 * (wave + NW * (c >> 1)) + (c & 1) : wave + NW * c;
-}
+// A wave's chunks come in adjacent pairs (2w, 2w + 1, 2w + 16, 2w + 17, ...), so the two loads it issues back to back
+// for a row cover one whole 128-B line (with single chunks c = w, w + 8, ... each 128-B line of a weight row was split
+// between two waves' loads, issued at different times).
+SD_DEV int core_chunk(int wave, int c) { return 2 * (wave + NW * (c >> 1)) + (c & 1); }
 template <int NT, int CPW>
 struct Core {
-  static_assert(!SD_CORE_PAIR || CPW % 2 == 0, "chunk pairs");
+  static_assert(CPW % 2 == 0, "chunk pairs");
   f32x4 b[CPW][NT];
   f32x4 acc[NT];
 
@@ -130,11 +129,9 @@ constexpr int core_lds_floats() { return NW * NT * 256 + MR * 16 * NT; }
 // XCD-contiguous tiles: the dispatcher deals workgroup i to XCD i % 8, so tile (i % 8) * (n / 8) + i / 8 gives XCD x
 // the n / 8 consecutive column tiles [x n / 8, (x + 1) n / 8) (with 16-column tiles over D = 2048: exactly block x).
 // Each XCD then writes whole 128-B lines of every output row (two or four neighbouring tiles share a line), and the
-// lines left dirty at the launch's end are not split between XCDs. Speed only: any tile order gives the same result.
-#ifndef SD_SCAN_XCD
-#define SD_SCAN_XCD 1
-#endif
-SD_DEV int xcd_tile(int i, int n) { return (SD_SCAN_XCD && n % 8 == 0) ? (i % 8) * (n / 8) + i / 8 : i; }
+// lines left dirty at the launch's end are not split between XCDs. Speed only: any tile order gives the same result
+// (a tile count that is no multiple of 8 keeps the dispatch order).
+SD_DEV int xcd_tile(int i, int n) { return n % 8 == 0 ? (i % 8) * (n / 8) + i / 8 : i; }
 
 // ------------------------------------------------------------------------------------------- load helpers
 // Prologues use 32 threads per row (16 rows): thread t32 owns the float4 columns c = 4*t32 + 128*i. Every load a
@@ -214,32 +211,14 @@ SD_DEV void st_row(float* rowp, const f32x4 (&v)[NI], int N, int t32) {
   }
 }
 
-constexpr int KSM = 8;         // max split-K slabs (ks_d, ks_s)
-#ifndef SD_LR_NG
-#define SD_LR_NG 8  // 4: 12.03 / 12.01 ms, 8: 11.98 / 11.95 ms per update (same box, profiles/r03ng_env.txt); again
-                    // on round-5 code, 4: 11.01 vs 8: 10.88 ms (k_logit_rows 6.2 -> 8.2 us, k_hid 6.9 -> 6.7, r05ng)
-#endif
-constexpr int LR_NG = SD_LR_NG;                 // x1p slabs written by k_logit_rows (categorical groups per row)
-constexpr int KS1 = LR_NG > KSM ? LR_NG : KSM;  // max x1p slabs k_hid sums
-constexpr int lr_cpg(int SK, int KD) { return SK / (LR_NG * KD) > 0 ? SK / (LR_NG * KD) : 1; }
-// output columns per workgroup of k_hid / k_gate: 16, or 8 (twice the workgroups, half the weight rows each; the
-// 16-wide MFMA tile then carries 8 zero weight rows in k_hid, and r|c + u|0 gate rows in k_gate)
-#ifndef SD_SCAN_HCW
-#define SD_SCAN_HCW 16
-#endif
-#ifndef SD_SCAN_GCW
-#define SD_SCAN_GCW 8
-#endif
-// output columns per workgroup of k_dlogit / k_dgru / k_dhh (16 or 8)
-#ifndef SD_SCAN_DLCW
-#define SD_SCAN_DLCW 16
-#endif
-#ifndef SD_SCAN_DGCW
-#define SD_SCAN_DGCW 16
-#endif
-#ifndef SD_SCAN_DHCW
-#define SD_SCAN_DHCW 16
-#endif
+constexpr int KSM = 8;    // max split-K slabs of the D-wide step GEMMs (ks_d)
+constexpr int LR_NG = 8;  // x1p slabs: the categorical groups per row of k_logit_rows (one slab each), summed by k_hid
+static_assert(LR_NG == KSM && KSM == 8, "k_hid sums LR_NG x1p slabs and up to KSM x0p slabs: 8 each");
+// categoricals per k_logit_rows workgroup: S / LR_NG (check() admits S = SK / Kd in {8, 16, 32, 64}, so >= 1)
+constexpr int lr_cpg(int SK, int KD) { return SK / (LR_NG * KD); }
+// Output columns per workgroup: 16 (one MFMA tile) in every kernel but k_gate, whose workgroups take 8 deter columns
+// (GCW) with their r | c and u gate rows as two tiles (DESIGN.md § 4.2 has the measurements).
+constexpr int GCW = 8;
 // ------------------------------------------------------------------------------------------- scratch layout
 struct Work {
   float *x0s, *x1s, *ops, *ssh, *dotp, *dxs, *dhin, *gq, *ch, *w1t;
@@ -255,10 +234,10 @@ Work work_layout(const sd_rssm_scan& d, float* base) {
   const long BU = (long)d.B * d.U;
   auto take = [&](long n) { float* p = base ? base + o : nullptr; o += al64(n); return p; };
   w.x0s = take(d.ks_d * BU);
-  w.x1s = take((long)KS1 * BU);  // ks_s slabs, or k_logit_rows' LR_NG
+  w.x1s = take((long)LR_NG * BU);
   w.ops = take(d.ks_d * BU);
-  w.ssh = take(NT * MR * (d.D / 8));  // per row tile: 16 rows x (D/16 or D/8 column tiles) partials
-  w.dotp = take(NT * MR * (d.D / 8));  // per row tile: 16 rows x (D/16 or D/8 column tiles) partials
+  w.ssh = take(NT * MR * (d.D / 8));   // per row tile: 16 rows x D/16 column-tile partials (sized for D/8 tiles)
+  w.dotp = take(NT * MR * (d.D / 8));  // the same
   w.dxs = take((long)d.G * d.B * 3 * d.U);
   w.dhin = take((long)d.B * d.D);
   w.gq = take((long)d.B * d.D);
@@ -329,9 +308,9 @@ __global__ void k_zero(float* p, long n) {
   if (i < n) p[i] = 0.f;
 }
 
-// (and w1t = W1^T for k_logit_rows)
+// and w1t = W1^T, k_logit_rows' gather rows
 __global__ void k_init(sd_rssm_scan d, float* w1t) {
-  const long nS = (long)d.B * d.SK, nD = (long)d.B * d.D, nW = w1t ? (long)d.SK * d.U : 0;
+  const long nS = (long)d.B * d.SK, nD = (long)d.B * d.D, nW = (long)d.SK * d.U;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nW; i += (long)gridDim.x * blockDim.x) {
     const long k = i / d.U, c = i % d.U;  // w1t[k][c] = W1[c][k]
     w1t[i] = d.W1[c * d.SK + k];
@@ -357,25 +336,27 @@ SD_DEV long in_row(const sd_rssm_scan& d, int t, int b) {
 }
 
 // X0F: x0 = silu(rms(x0p)) was formed by the previous step's k_logit_rows (written into xcat), read as it stands;
-// otherwise (t = 0, or the k_logit path) summed from the split-K slabs and normalised here. CW: output columns per
-// workgroup (16 or 8; grid D / CW), the row partials of hp^2 then come per CW-column tile.
-template <int CPW, int NG, bool X0F, int CW>
+// otherwise (t = 0) summed from the split-K slabs and normalised here. x1p is always the sum of LR_NG slabs (step 0's
+// from k_slab, later ones from the previous step's k_logit_rows); the count arrives in the launch's own copy of the
+// descriptor (d.ks_s, written by fwd_phase; the caller's ks_s is not read), a run-time value like ks_d: with a
+// literal count hipcc allocates the kernel differently (k_hid<8, 2, true> 122 -> 130 VGPRs).
+template <int CPW, int NG, bool X0F>
 __global__ __launch_bounds__(NTHR) void k_hid(sd_rssm_scan d, Work w, int t) {
   extern __shared__ float smem[];
   SD_TR_BEGIN
   SD_THREAD_IDS
   SD_ROW_TILE
   const int B = d.B, D = d.D, Dg = D / d.G, Ig = Dg + 3 * UH, ldp = Ig + 4;
-  const int tile = xcd_tile(blockIdx.x, gridDim.x), n0 = tile * CW, g = n0 / Dg;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x), n0 = tile * 16, g = n0 / Dg;
   Core<1, CPW> core;
-  const float* wt[1] = {d.Wh + (long)(n0 + (l16 & (CW - 1))) * Ig};  // CW 8: lanes 8..15 repeat rows (discarded)
+  const float* wt[1] = {d.Wh + (long)(n0 + l16) * Ig};
   core.load_b(wt, Ig / 16, wave, q);
   const int row = tid >> 5, t32 = tid & 31, gr = rb + row;
   const bool rv = row < nr;
   const int grc = rv ? gr : rb + nr - 1;  // rows past the tile read the tile's last row (results discarded)
   const long tBU = (long)t * B * UH;
   f32x4 h[NG], x0[NU], x1[NU], x2v[NU], b0v[NU], b1v[NU], n0v[NU], n1v[NU];
-  f32x4 x0p[X0F ? 1 : KSM][NU], x1p[KS1][NU];
+  f32x4 x0p[X0F ? 1 : KSM][NU], x1p[LR_NG][NU];
   ld_row(h, d.h_in + (long)t * B * D + (long)grc * D + (long)g * Dg, t32);
   if constexpr (X0F) {
     ld_row(x0, d.xcat + 3 * tBU + (long)grc * 3 * UH, t32);
@@ -384,12 +365,12 @@ __global__ __launch_bounds__(NTHR) void k_hid(sd_rssm_scan d, Work w, int t) {
     ld_row(b0v, d.b0, t32);
     ld_row(n0v, d.n0, t32);
   }
-  ld_slabs<NU, KS1>(x1p, w.x1s + (long)grc * UH, (long)B * UH, d.ks_s, t32);
+  ld_slabs<NU, LR_NG>(x1p, w.x1s + (long)grc * UH, (long)B * UH, d.ks_s, t32);  // (= LR_NG, set by fwd_phase)
   ld_row(b1v, d.b1, t32);
   ld_row(n1v, d.n1, t32);
   ld_row(x2v, d.x2 + in_row(d, t, grc) * UH, t32);
   const int ec = tid & 15;
-  const float bhv = d.bh[n0 + (ec & (CW - 1))];
+  const float bhv = d.bh[n0 + ec];
   // every load is in flight: now the prologue arithmetic
   f32x4 y0[NU], y1[NU];
   float r0 = 0.f;
@@ -435,57 +416,52 @@ __global__ __launch_bounds__(NTHR) void k_hid(sd_rssm_scan d, Work w, int t) {
   SD_TR(2)
   if (tid < 256) {
     const int er = tid >> 4, c = tid & 15;
-    const bool ok = er < nr && (CW == 16 || c < CW);
+    const bool ok = er < nr;
     const float v = C[er * 16 + c] + bhv;
     if (ok) d.hp[(long)t * B * D + (long)(rb + er) * D + n0 + c] = v;
     const float ss = group_sum<16>(ok ? v * v : 0.f);
-    if (c == 0) w.ssh[((long)blockIdx.z * MR + er) * (D / CW) + tile] = ss;
+    if (c == 0) w.ssh[((long)blockIdx.z * MR + er) * (D / 16) + tile] = ss;
   }
   SD_TR_END(d.trace, d.trace_slot)
 }
 
 // gates = BlockLinear(dyn_gru)(silu(rms(hp))) + bg; deter = GRU(gates, h_in) (rssm.py:65-75); h_in[t+1] masked.
-// grid (D/CW): workgroup = CW deter columns of one block with their r / c / u gate rows: CW 16 = 3 MFMA tiles (r, c,
-// u); CW 8 = 2 tiles (r | c, u | zero rows). HCW: k_hid's column tile (D / HCW row partials of hp^2 per row).
-template <int CPW, int NG, int CW, int HCW>
+// grid (D/8): workgroup = GCW = 8 deter columns of one block with their r / c / u gate rows as 2 MFMA tiles (r | c,
+// u | u again: twice the workgroups of a 16-column form with 3 tiles, half the weight rows each). The row partials of
+// hp^2 come from k_hid's D / 16 column tiles.
+template <int CPW, int NG>
 __global__ __launch_bounds__(NTHR) void k_gate(sd_rssm_scan d, Work w, int t) {
   extern __shared__ float smem[];
   SD_TR_BEGIN
   SD_THREAD_IDS
   SD_ROW_TILE
-  constexpr int NTL = CW == 16 ? 3 : 2, CL = 16 * NTL;
+  constexpr int CW = GCW, NTL = 2, CL = 16 * NTL;
   const int B = d.B, D = d.D, Dg = D / d.G, ldp = Dg + 4;
   const int tile = xcd_tile(blockIdx.x, gridDim.x), n0 = tile * CW, g = n0 / Dg, j0 = n0 % Dg;
   Core<NTL, CPW> core;
   const float* wg = d.Wg + (long)g * 3 * Dg * Dg;
-  const float* wt[NTL];
-  if constexpr (CW == 16) {
-    wt[0] = wg + (long)(j0 + l16) * Dg;
-    wt[1] = wg + (long)(Dg + j0 + l16) * Dg;
-    wt[NTL - 1] = wg + (long)(2 * Dg + j0 + l16) * Dg;
-  } else {  // tile 1's lanes 8..15 repeat the u rows (their output columns are discarded)
-    wt[0] = wg + (long)(l16 < 8 ? j0 + l16 : Dg + j0 + l16 - 8) * Dg;
-    wt[NTL - 1] = wg + (long)(2 * Dg + j0 + (l16 & 7)) * Dg;
-  }
+  // tile 0: r rows | c rows; tile 1: u rows, lanes 8..15 repeat them (their output columns are discarded)
+  const float* wt[NTL] = {wg + (long)(l16 < 8 ? j0 + l16 : Dg + j0 + l16 - 8) * Dg,
+                          wg + (long)(2 * Dg + j0 + (l16 & 7)) * Dg};
   core.load_b(wt, Dg / 16, wave, q);
   const int row = tid >> 5, t32 = tid & 31, gr = rb + row;
   const bool rv = row < nr;
   const int grc = rv ? gr : rb + nr - 1;
-  constexpr int NPP = (4096 / HCW + 127) / 128;  // float4 partial loads per thread (D <= 4096)
+  constexpr int NPP = (4096 / 16 + 127) / 128;  // float4 partial loads per thread (D <= 4096)
   f32x4 pv[NPP];
-  ld_parts(pv, w.ssh + ((long)blockIdx.z * MR + row) * (D / HCW), D / HCW, t32);
+  ld_parts(pv, w.ssh + ((long)blockIdx.z * MR + row) * (D / 16), D / 16, t32);
   f32x4 hv[NG], nv[NG];
   ld_row(hv, d.hp + (long)t * B * D + (long)grc * D + (long)g * Dg, t32);
   ld_row(nv, d.nh + (long)g * Dg, t32);
   // epilogue operands (thread = (row er, column c < CW)), read unconditionally at clamped indices
   const int er = (tid >> 4) & 15, c = tid & 15, j = j0 + c, col = n0 + c, ger = rb + er;
-  const bool ev = tid < 256 && er < nr && (CW == 16 || c < CW);
+  const bool ev = tid < 256 && er < nr && c < CW;
   const int cc_ = c & (CW - 1), gerc = er < nr ? ger : rb + nr - 1;
   const float* bg = d.bg + (long)g * 3 * Dg;
   const float bra = bg[j0 + cc_], bca = bg[Dg + j0 + cc_], bua = bg[2 * Dg + j0 + cc_];
   const float hprev = d.h_in[(long)t * B * D + (long)gerc * D + n0 + cc_];
   const unsigned char rflag = reset_byte(d, t + 1, gerc);
-  const float r = rsqrtf(sum_parts(pv, D / HCW, t32) / (float)D + d.eps);
+  const float r = rsqrtf(sum_parts(pv, D / 16, t32) / (float)D + d.eps);
   if (rv && t32 == 0 && tile == 0) d.rh[(long)t * B + gr] = r;
   f32x4 y[NG];
 #pragma unroll
@@ -502,8 +478,8 @@ __global__ __launch_bounds__(NTHR) void k_gate(sd_rssm_scan d, Work w, int t) {
   SD_TR(2)
   if (ev) {
     const float ra = C[er * CL + c] + bra;
-    const float ca = C[er * CL + (CW == 16 ? 16 : 8) + c] + bca;
-    const float ua = C[er * CL + (CW == 16 ? 32 : 16) + c] + bua;
+    const float ca = C[er * CL + 8 + c] + bca;
+    const float ua = C[er * CL + 16 + c] + bua;
     float* gw = d.gates + (long)t * B * 3 * D + (long)ger * 3 * D + (long)g * 3 * Dg;
     gw[j] = ra;
     gw[Dg + j] = ca;
@@ -519,90 +495,14 @@ __global__ __launch_bounds__(NTHR) void k_gate(sd_rssm_scan d, Work w, int t) {
   SD_TR_END(d.trace, d.trace_slot)
 }
 
-// logits = obs_net_logit(silu(rms(op))) and the straight-through unimix one-hot sample (rssm.py:172-177,
-// distributions.py:16-33); op = sum of the obs_net_0 slabs + (embed half + bias). grid (S): one categorical / WG.
-template <int KD>
-__global__ __launch_bounds__(NTHR) void k_logit(sd_rssm_scan d, Work w, int t) {
-  extern __shared__ float smem[];
-  SD_THREAD_IDS
-  SD_ROW_TILE
-  constexpr int NT = KD / 16, NE = (MR * KD + NTHR - 1) / NTHR;
-  const int B = d.B, SK = d.SK, S = SK / KD, ldp = UH + 4;
-  const int s = blockIdx.x, n0 = s * KD;
-  Core<NT, 2> core;
-  const float* wt[NT];
-#pragma unroll
-  for (int i = 0; i < NT; ++i) wt[i] = d.Wl + (long)(n0 + 16 * i + l16) * UH;
-  core.load_b(wt, UH / 16, wave, q);
-  const int row = tid >> 5, t32 = tid & 31, gr = rb + row;
-  const bool rv = row < nr;
-  const int grc = rv ? gr : rb + nr - 1;
-  const long tBU = (long)t * B * UH;
-  f32x4 x[NU], e[NU], nv[NU], xs[KSM][NU];
-  ld_slabs<NU, KSM>(xs, w.ops + (long)grc * UH, (long)B * UH, d.ks_d, t32);
-  ld_row(e, d.eproj + in_row(d, t, grc) * UH, t32);
-  ld_row(nv, d.no, t32);
-  sum_slabs(x, xs, d.ks_d);
-  // sampler operands + noise, independent of the contraction
-  const uint64_t seed = d.seed + (d.seed_ptr ? *d.seed_ptr : 0ull);
-  float blv[NE], gn[NE];
-  bool rnext[NE];
-#pragma unroll
-  for (int k = 0; k < NE; ++k) {
-    const int i = tid + NTHR * k, er = (i / KD) & 15, lt = i % KD;
-    blv[k] = d.bl[n0 + lt];
-    gn[k] = sd_gumbel(seed, (uint32_t)d.stream_id, (uint32_t)t,
-                      (uint64_t)((long)(rb + er) * S + s + d.group_offset) * KD + lt);
-    rnext[k] = er < nr && t + 1 < d.T && reset_at(d, t + 1, rb + er);
-  }
-#pragma unroll
-  for (int i = 0; i < NU; ++i) x[i] += e[i];
-  f32x4 y[NU];
-  const float r = rms_silu_rows(x, nv, UH, d.eps, rv, y);
-  st_row(smem + core_lds_floats<NT>() + row * ldp, y, UH, t32);
-  if (rv && s == 0) {
-    st_row(d.op + tBU + (long)gr * UH, x, UH, t32);
-    st_row(d.oo + tBU + (long)gr * UH, y, UH, t32);
-    if (t32 == 0) d.ro[(long)t * B + gr] = r;
-  }
-  __syncthreads();
-  core.run_lds(smem + core_lds_floats<NT>(), ldp, UH / 16, wave, l16, q);
-  float* C = smem + NW * NT * 256;
-  core.reduce(smem, C, tid, wave, lane);
-#pragma unroll
-  for (int k = 0; k < NE; ++k) {  // team of KD lanes per (row, categorical)
-    const int i = tid + NTHR * k;
-    if (i < MR * KD) {
-      const int er = i / KD, lt = i % KD;
-      const float l = C[er * KD + lt] + blv[k];
-      float p, pp, nl;
-      unimix_forward<KD>(l, true, KD, d.unimix, p, pp, nl);
-      float ys;
-      int idx;
-      st_soft<KD>(nl, gn[k], true, ys, idx, lt);
-      if (er < nr) {
-        const float yv = ((lt == idx ? 1.f : 0.f) - ys) + ys;
-        const long o = (long)t * B * SK + (long)(rb + er) * SK + n0 + lt;
-        d.logit[o] = l;
-        if (d.stoch) d.stoch[o] = yv;
-        if (d.post_logit) {  // batch-major copies (RSSM.observe's outputs)
-          const long ob = ((long)(rb + er) * d.T + t) * SK + n0 + lt;
-          d.post_logit[ob] = l;
-          d.post_stoch[ob] = yv;
-        }
-        if (t + 1 < d.T) d.s_in[o + (long)B * SK] = rnext[k] ? 0.f : yv;
-      }
-    }
-  }
-}
-
-// k_logit by rows, with the next step's _dyn_in1 folded in: workgroup (g, b) takes batch row b and the CPG
+// logits = obs_net_logit(silu(rms(op))), op = sum of the obs_net_0 slabs + (embed half + bias), by rows, with the next
+// step's _dyn_in1 folded in. grid (LR_NG, B): workgroup (g, b) takes batch row b and the CPG = S / LR_NG
 // categoricals g*CPG.. of the obs_net logits (rssm.py:172-177): obs_net RMSNorm + SiLU of its row, the CPG*KD logits
 // (fp32 dot products, K = U split over TPC lanes), the unimix one-hot ST sample (distributions.py:16-33), and then
 // slab g of x1p[t+1] = the sample's _dyn_in1 pre-activation (rssm.py:52-56). A straight-through one-hot row holds one
 // nonzero per categorical (((k == idx) - ys) + ys is exactly 0 off the index), so its contraction with W1 is a gather
-// of CPG rows of W1^T: the NG = S / CPG slabs of a row sum (in k_hid's prologue, fixed order) to the dense product.
-// That removes the x1p k_slab launch from every step (4 dependent launches per step instead of 5).
+// of CPG rows of W1^T: the LR_NG slabs of a row sum (in k_hid's prologue, fixed order) to the dense product.
+// That removes the x1p k_slab launch from every step but the first (4 dependent launches per step instead of 5).
 template <int KD, int CPG>
 __global__ __launch_bounds__(NTHR) void k_logit_rows(sd_rssm_scan d, Work w, int t) {
   constexpr int NC = CPG * KD, TPC = NTHR / NC, KPT = UH / TPC, NQ = KPT / 4;
@@ -822,17 +722,17 @@ __global__ __launch_bounds__(256) void k_sbwd_last(sd_rssm_scan d) {
   if (v) d.dl[o] = in_grad(d, d.d_logit, nullptr, t, row, k, SK) + dl;
 }
 
-// d_o = dl[t] . Wl   (dl built by the previous launch). grid (U/CW)
-template <int CPW, int NS, int CW>
+// d_o = dl[t] . Wl   (dl built by the previous launch). grid (U/16)
+template <int CPW, int NS>
 __global__ __launch_bounds__(NTHR) void k_dlogit(sd_rssm_scan d, Work w, int t) {
   extern __shared__ float smem[];
   SD_TR_BEGIN
   SD_THREAD_IDS
   SD_ROW_TILE
   const int B = d.B, SK = d.SK, ldp = SK + 4;
-  const int n0 = xcd_tile(blockIdx.x, gridDim.x) * CW;
+  const int n0 = xcd_tile(blockIdx.x, gridDim.x) * 16;
   Core<1, CPW> core;
-  const float* wt[1] = {d.WlT + (long)(n0 + (l16 & (CW - 1))) * SK};
+  const float* wt[1] = {d.WlT + (long)(n0 + l16) * SK};
   core.load_b(wt, SK / 16, wave, q);
   const int row = tid >> 5, t32 = tid & 31;
   f32x4 v[NS];
@@ -846,23 +746,22 @@ __global__ __launch_bounds__(NTHR) void k_dlogit(sd_rssm_scan d, Work w, int t) 
   SD_TR(2)
   if (tid < 256) {
     const int er = tid >> 4, c = tid & 15;
-    if (er < nr && (CW == 16 || c < CW)) d.d_o[(long)t * B * UH + (long)(rb + er) * UH + n0 + c] = C[er * 16 + c];
+    if (er < nr) d.d_o[(long)t * B * UH + (long)(rb + er) * UH + n0 + c] = C[er * 16 + c];
   }
   SD_TR_END(d.trace, d.trace_slot)
 }
 
 // d_op = RMSNorm-SiLU backward (prologue); dh = d_deter + carry_h + d_op . Wo[:, :D]; GRU backward (epilogue).
-// grid (D/CW)
-template <int CW>
+// grid (D/16)
 __global__ __launch_bounds__(NTHR) void k_dgru(sd_rssm_scan d, Work w, int t) {
   extern __shared__ float smem[];
   SD_TR_BEGIN
   SD_THREAD_IDS
   SD_ROW_TILE
   const int B = d.B, D = d.D, Dg = D / d.G, ldp = UH + 4;
-  const int tile = xcd_tile(blockIdx.x, gridDim.x), n0 = tile * CW;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x), n0 = tile * 16;
   Core<1, 2> core;
-  const float* wt[1] = {d.WoDT + (long)(n0 + (l16 & (CW - 1))) * UH};
+  const float* wt[1] = {d.WoDT + (long)(n0 + l16) * UH};
   core.load_b(wt, UH / 16, wave, q);
   const int row = tid >> 5, t32 = tid & 31, gr = rb + row;
   const bool rv = row < nr;
@@ -874,9 +773,9 @@ __global__ __launch_bounds__(NTHR) void k_dgru(sd_rssm_scan d, Work w, int t) {
   ld_row(nv, d.no, t32);
   const float r_ = d.ro[(long)t * B + grc];
   // epilogue operands, read unconditionally at clamped indices
-  const int er = (tid >> 4) & 15, c = tid & 15, col = n0 + (c & (CW - 1)), g = col / Dg, j = col % Dg;
+  const int er = (tid >> 4) & 15, c = tid & 15, col = n0 + c, g = col / Dg, j = col % Dg;
   const int ger = er < nr ? rb + er : rb + nr - 1;
-  const bool ev = tid < 256 && er < nr && (CW == 16 || c < CW);
+  const bool ev = tid < 256 && er < nr;
   const long od = (long)t * B * D + (long)ger * D + col;
   const long gb = (long)t * B * 3 * D + (long)ger * 3 * D + (long)g * 3 * Dg;
   InGrad ig;
@@ -927,21 +826,21 @@ __global__ __launch_bounds__(NTHR) void k_dgru(sd_rssm_scan d, Work w, int t) {
 }
 
 // d_hh = d_gates_g . Wg[g] (block GEMM); epilogue: RMSNorm-SiLU backward pieces of dyn_hid's norm (g*w and the
-// per-tile row partials of sum g*xhat). grid (D/CW)
-template <int CPW, int CW>
+// per-tile row partials of sum g*xhat). grid (D/16)
+template <int CPW>
 __global__ __launch_bounds__(NTHR) void k_dhh(sd_rssm_scan d, Work w, int t) {
   extern __shared__ float smem[];
   SD_TR_BEGIN
   SD_THREAD_IDS
   SD_ROW_TILE
   const int B = d.B, D = d.D, Dg = D / d.G;
-  const int tile = xcd_tile(blockIdx.x, gridDim.x), n0 = tile * CW, g = n0 / Dg, j0 = n0 % Dg;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x), n0 = tile * 16, g = n0 / Dg, j0 = n0 % Dg;
   Core<1, CPW> core;
-  const float* wt[1] = {d.WgT + ((long)g * Dg + j0 + (l16 & (CW - 1))) * 3 * Dg};
+  const float* wt[1] = {d.WgT + ((long)g * Dg + j0 + l16) * 3 * Dg};
   core.load_b(wt, 3 * Dg / 16, wave, q);
-  const int er = (tid >> 4) & 15, c = tid & 15, col = n0 + (c & (CW - 1));
+  const int er = (tid >> 4) & 15, c = tid & 15, col = n0 + c;
   const int ger = er < nr ? rb + er : rb + nr - 1;
-  const bool ev = tid < 256 && er < nr && (CW == 16 || c < CW);
+  const bool ev = tid < 256 && er < nr;
   const long o = (long)t * B * D + (long)ger * D + col;
   const float hpv = d.hp[o], rhv = d.rh[(long)t * B + ger], wv = d.nh[col];  // unconditional, clamped
   core.run_glb(d.d_gates + ((long)t * B + rb) * 3 * D + (long)g * 3 * Dg, 3 * (long)D, nr, 3 * Dg / 16, wave, l16, q);
@@ -960,61 +859,49 @@ __global__ __launch_bounds__(NTHR) void k_dhh(sd_rssm_scan d, Work w, int t) {
       part = gq * xh;
     }
     part = group_sum<16>(part);
-    if (c == 0) w.dotp[((long)blockIdx.z * MR + er) * (D / CW) + tile] = part;
+    if (c == 0) w.dotp[((long)blockIdx.z * MR + er) * (D / 16) + tile] = part;
   }
   SD_TR_END(d.trace, d.trace_slot)
 }
 
-// d_xcat slabs k_dhp writes: slab s covers G / KX consecutive blocks (KX = 8 = G: one per block). Fewer slabs mean
-// fewer, larger P0 workgroups and less for k_carry to stage (each of its workgroups sums KX slabs of 16 rows)
-#ifndef SD_SCAN_KX
-#define SD_SCAN_KX 8
-#endif
-__host__ __device__ inline int kx_of(int G) { return G % SD_SCAN_KX == 0 ? SD_SCAN_KX : G; }
-
-// d_hp = RMSNorm backward (prologue, from g*w and the row partials) over the workgroup's K span; then two problems in
-// one grid:
-//   P0: d_xcat slab s = d_hp[:, blocks of s] . Wsh[those rows]   ((3U/16) * KX workgroups, K = G/KX blocks)
-//   P1: d_hin[:, g] += d_hp_g . Wbd[g]                            (D/16 workgroups, K = one block)
-// CPW / NGX cover the longest span (P0); P1 masks the chunks past its block. DHC: k_dhh's column tile (D / DHC row
-// partials).
-template <int CPW, int NGX, int DHC>
+// d_hp = RMSNorm backward (prologue, from g*w and k_dhh's D / 16 row partials) over the workgroup's block (K = D/G =
+// 128 * NGX); then two problems in one grid:
+//   P0: d_xcat slab g = d_hp_g . Wsh[rows of block g]   ((3U/16) * G workgroups: one d_xcat slab per block)
+//   P1: d_hin[:, g] += d_hp_g . Wbd[g]                   (D/16 workgroups)
+template <int CPW, int NGX>
 __global__ __launch_bounds__(NTHR) void k_dhp(sd_rssm_scan d, Work w, int t) {
   extern __shared__ float smem[];
   SD_TR_BEGIN
   SD_THREAD_IDS
   SD_ROW_TILE
-  const int B = d.B, D = d.D, Dg = D / d.G, X = 3 * UH;
-  const int KX = kx_of(d.G), NX = (X / 16) * KX;
+  const int B = d.B, D = d.D, Dg = D / d.G, X = 3 * UH, K = Dg, ldp = K + 4;
+  const int NX = (X / 16) * d.G;
   const int blk = blockIdx.x;
   const bool p0 = blk < NX;
-  int n0, k0, K, sl = 0;
+  int n0, k0, sl = 0;
   const float* wrow;
   if (p0) {  // (X / 16 = 48 column tiles per slab: blk % 8 = tile % 8, so the remap stays within a slab)
     sl = blk / (X / 16);
     n0 = xcd_tile(blk % (X / 16), X / 16) * 16;
-    K = (d.G / KX) * Dg;
-    k0 = sl * K;
+    k0 = sl * Dg;
     wrow = d.WshT + (long)(n0 + l16) * D + k0;
-  } else {  // (NX = 48 KX is a multiple of 8)
+  } else {  // (NX = 48 G is a multiple of 8)
     n0 = xcd_tile(blk - NX, D / 16) * 16;
     const int g = n0 / Dg;
-    K = Dg;
     k0 = g * Dg;
     wrow = d.WbdT + ((long)g * Dg + n0 % Dg + l16) * Dg;
   }
-  const int ldp = K + 4;
   Core<1, CPW> core;
   const float* wt[1] = {wrow};
   core.load_b(wt, K / 16, wave, q);
   const int row = tid >> 5, t32 = tid & 31, gr = rb + row;
   const bool rv = row < nr;
-  constexpr int NPP = (4096 / DHC + 127) / 128;
+  constexpr int NPP = (4096 / 16 + 127) / 128;
   f32x4 pv[NPP];
-  ld_parts(pv, w.dotp + ((long)blockIdx.z * MR + row) * (D / DHC), D / DHC, t32);
+  ld_parts(pv, w.dotp + ((long)blockIdx.z * MR + row) * (D / 16), D / 16, t32);
   const int grc = rv ? gr : rb + nr - 1;
   const long ob = (long)gr * D + k0, obc = (long)grc * D + k0;
-  f32x4 gq[NGX], xv[NGX];  // (K = D/G = 128 * NGX on both problems: G / KX = 1)
+  f32x4 gq[NGX], xv[NGX];
   ld_row(gq, w.gq + obc, t32);
   ld_row(xv, d.hp + (long)t * B * D + obc, t32);
   const float r_ = d.rh[(long)t * B + grc];
@@ -1022,7 +909,7 @@ __global__ __launch_bounds__(NTHR) void k_dhp(sd_rssm_scan d, Work w, int t) {
   const bool ev = tid < 256 && er < nr;
   const float dh_ = w.dhin[(long)(er < nr ? ger : rb + nr - 1) * D + n0 + c];  // unconditional, used by P1 only
   const float r = rv ? r_ : 0.f, dh_old = (!p0 && ev) ? dh_ : 0.f;
-  const float dot = sum_parts(pv, D / DHC, t32) / (float)D;
+  const float dot = sum_parts(pv, D / 16, t32) / (float)D;
   f32x4 o[NGX];
 #pragma unroll
   for (int i = 0; i < NGX; ++i)
@@ -1058,7 +945,7 @@ __global__ __launch_bounds__(NTHR) void k_dx01(sd_rssm_scan d, Work w, int t) {
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
       const int c = tid + NTHR * k;
-      part[g][k] = (g < kx_of(d.G) && c < X) ? w.dxs[(long)g * B * X + (long)b * X + c] : 0.f;
+      part[g][k] = (g < d.G && c < X) ? w.dxs[(long)g * B * X + (long)b * X + c] : 0.f;
     }
   const int half = wave >> 2, ht = tid & 255;
   const float* x = (half ? d.x1p : d.x0p) + (tB + b) * UH;
@@ -1104,7 +991,7 @@ __global__ __launch_bounds__(NTHR) void k_carry(sd_rssm_scan d, Work w, int t) {
   constexpr int NT = KD / 16, NE = (MR * KD + NTHR - 1) / NTHR, GM = 8, X = 3 * UH, ldp = UH + 4;
   const int B = d.B, D = d.D, SK = d.SK, S = SK / KD;
   if ((int)blockIdx.x == D / KD + SK / KD) {  // the x2 part of d_xcat: sum of k_dhp's slabs (k_dx01's order)
-    const int row = tid >> 5, t32 = tid & 31, gr = rb + row, KX = kx_of(d.G);
+    const int row = tid >> 5, t32 = tid & 31, gr = rb + row, KX = d.G;  // one d_xcat slab per block
     const int grc = row < nr ? gr : rb + nr - 1;
     const long tB = (long)t * B;
     f32x4 part2[GM][NU], dx[NU];
@@ -1131,7 +1018,7 @@ __global__ __launch_bounds__(NTHR) void k_carry(sd_rssm_scan d, Work w, int t) {
   // clamped; slabs past KX re-read slab KX - 1 and are not summed)
   const int row = tid >> 5, t32 = tid & 31, gr = rb + row;
   const bool rv = row < nr;
-  const int grc = rv ? gr : rb + nr - 1, KX = kx_of(d.G);
+  const int grc = rv ? gr : rb + nr - 1, KX = d.G;  // one d_xcat slab per block
   const long tB = (long)t * B;
   const int hoff = p0 ? 0 : UH;
   f32x4 part[GM][NU], xv[NU], nv[NU];
@@ -1271,9 +1158,7 @@ int check(const sd_rssm_scan* d) {
   if (d->U != UH || (Dg != 256 && Dg != 512) || (d->SK != 512 && d->SK != 1024) || d->D > 4096) return SD_ESHAPE;
   if (d->Kd != 16 && d->Kd != 32 && d->Kd != 64) return SD_ESHAPE;
   if (d->SK % d->Kd || d->D % d->Kd) return SD_ESHAPE;
-  if (d->ks_d < 1 || d->ks_s < 1 || d->ks_d > KSM || d->ks_s > KSM || d->D % (d->ks_d * 16) ||
-      d->SK % (d->ks_s * 16))
-    return SD_ESHAPE;
+  if (d->ks_d < 1 || d->ks_d > KSM || d->D % (d->ks_d * 16)) return SD_ESHAPE;  // (ks_s is reserved, not read)
   if (!d->work) return SD_EARG;
   if (d->ld_wod < 0 || (d->ld_wod > 0 && (d->ld_wod < d->D || d->ld_wod % 4))) return SD_EARG;
   if ((d->post_logit != nullptr) != (d->post_stoch != nullptr)) return SD_EARG;
@@ -1288,43 +1173,36 @@ int check(const sd_rssm_scan* d) {
     default: return SD_ESHAPE;                                \
   }
 
-#ifndef SD_SCAN_LROWS
-#define SD_SCAN_LROWS 1
-#endif
-// the forward's per-step phases (0: x1p k_slab, 1: k_hid, 2: k_gate, 3: obs_net_0 + next x0p k_slab, 4: logits +
-// sampler [+ next x1p slabs when lrows]); one definition for sd_rssm_scan_fwd and the measurement aid
-int fwd_phase(const sd_rssm_scan& d, const Work& w, bool lrows, int which, int t, hipStream_t st) {
+// the forward's per-step phases (0: x1p k_slab [step 0 only in a run], 1: k_hid, 2: k_gate, 3: obs_net_0 + next x0p
+// k_slab, 4: logits + sampler + next x1p slabs); one definition for sd_rssm_scan_fwd and the measurement aid
+int fwd_phase(const sd_rssm_scan& d, const Work& w, int which, int t, hipStream_t st) {
   const int B = d.B, D = d.D, SK = d.SK, Dg = D / d.G, Ig = Dg + 3 * UH;
-  const int ks_s = lrows ? LR_NG : d.ks_s;
-  const int span_d = D / d.ks_d, span_s = SK / ks_s;
+  const int span_d = D / d.ks_d, span_s = SK / LR_NG;
   const int cp_d = cpw_for(span_d), cp_s = cpw_for(span_s), cp_h = cpw_for(Ig);
   if (cp_d < 0 || cp_s < 0 || cp_h < 0) return SD_ESHAPE;
   const size_t core1 = core_lds_floats<1>() * 4;
   const size_t lds_hid = core1 + (size_t)MR * (Ig + 4) * 4;
-  const size_t lds_gate = core_lds_floats<SD_SCAN_GCW == 16 ? 3 : 2>() * 4 + (size_t)MR * (Dg + 4) * 4;
+  const size_t lds_gate = core_lds_floats<2>() * 4 + (size_t)MR * (Dg + 4) * 4;
   const long BD = (long)B * D, BS = (long)B * SK;
   const long wod_ld = d.ld_wod > 0 ? d.ld_wod : D;
   sd_rssm_scan dd = d;
-  dd.ks_s = ks_s;  // x1p slabs k_hid sums
+  dd.ks_s = LR_NG;  // the x1p slabs k_hid sums (the launches' own copy: the caller's ks_s is reserved, not read)
   const int rt = dd.row_tile = row_tile_of(d), nt = row_tiles(d);
   dd.trace_slot = t * 8 + which;
-  if (which == 0) {
+  if (which == 0) {  // x1p slabs as k_logit_rows writes them for every later step: LR_NG spans of s_in[t] . W1^T
     SlabProb p{d.s_in + t * BS, SK, d.W1, SK, w.x1s, d.reset, d.trace, dd.trace_slot, 1, 0};
-    SD_CPW_SWITCH(cp_s, k_slab<CP><<<dim3(UH / 16, ks_s * nt, 1), NTHR, core1, st>>>(p, p, B, UH, span_s, ks_s, rt));
+    SD_CPW_SWITCH(cp_s, k_slab<CP><<<dim3(UH / 16, LR_NG * nt, 1), NTHR, core1, st>>>(p, p, B, UH, span_s, LR_NG, rt));
   } else if (which == 1) {
-    // x0 finished by the previous step's k_logit_rows (lrows, t > 0)
-    constexpr int HC = SD_SCAN_HCW;
-    if (lrows && t > 0) {
-      SD_NG_SWITCH(Dg, SD_CPW_SWITCH(cp_h, if (!(raise_lds<k_hid<CP, NG, true, HC>>(lds_hid))) return SD_EARG;
-                                     k_hid<CP, NG, true, HC><<<dim3(D / HC, 1, nt), NTHR, lds_hid, st>>>(dd, w, t)));
+    if (t > 0) {  // x0 finished by the previous step's k_logit_rows
+      SD_NG_SWITCH(Dg, SD_CPW_SWITCH(cp_h, if (!(raise_lds<k_hid<CP, NG, true>>(lds_hid))) return SD_EARG;
+                                     k_hid<CP, NG, true><<<dim3(D / 16, 1, nt), NTHR, lds_hid, st>>>(dd, w, t)));
     } else {
-      SD_NG_SWITCH(Dg, SD_CPW_SWITCH(cp_h, if (!(raise_lds<k_hid<CP, NG, false, HC>>(lds_hid))) return SD_EARG;
-                                     k_hid<CP, NG, false, HC><<<dim3(D / HC, 1, nt), NTHR, lds_hid, st>>>(dd, w, t)));
+      SD_NG_SWITCH(Dg, SD_CPW_SWITCH(cp_h, if (!(raise_lds<k_hid<CP, NG, false>>(lds_hid))) return SD_EARG;
+                                     k_hid<CP, NG, false><<<dim3(D / 16, 1, nt), NTHR, lds_hid, st>>>(dd, w, t)));
     }
   } else if (which == 2) {
-    constexpr int GC = SD_SCAN_GCW, HC = SD_SCAN_HCW;
-    SD_NG_SWITCH(Dg, if (!(raise_lds<k_gate<NG, NG, GC, HC>>(lds_gate))) return SD_EARG;
-                 k_gate<NG, NG, GC, HC><<<dim3(D / GC, 1, nt), NTHR, lds_gate, st>>>(dd, w, t));
+    SD_NG_SWITCH(Dg, if (!(raise_lds<k_gate<NG, NG>>(lds_gate))) return SD_EARG;
+                 k_gate<NG, NG><<<dim3(D / GCW, 1, nt), NTHR, lds_gate, st>>>(dd, w, t));
   } else if (which == 3) {
     SlabProb po{d.deter + t * BD, D, d.WoD, wod_ld, w.ops, d.reset, d.trace, dd.trace_slot, 1, 0};
     SlabProb px{d.deter + t * BD, D, d.W0, D, w.x0s, d.reset_bm ? d.reset + (t + 1) : d.reset + (t + 1) * B, d.trace,
@@ -1332,25 +1210,17 @@ int fwd_phase(const sd_rssm_scan& d, const Work& w, bool lrows, int which, int t
     const int np = t + 1 < d.T ? 2 : 1;
     SD_CPW_SWITCH(cp_d, k_slab<CP><<<dim3(UH / 16, d.ks_d * nt, np), NTHR, core1, st>>>(po, px, B, UH, span_d,
                                                                                         d.ks_d, rt));
-  } else if (lrows) {
+  } else {
     const dim3 gr(LR_NG, B);
 #define SD_LR(KD_, CPG_) k_logit_rows<KD_, CPG_><<<gr, NTHR, 0, st>>>(dd, w, t)
-    // CPG = S / LR_NG categoricals per workgroup (use_lrows: S % LR_NG == 0, so CPG >= 1 where it launches)
     if (d.Kd == 16) { if (SK == 512) SD_LR(16, lr_cpg(512, 16)); else SD_LR(16, lr_cpg(1024, 16)); }
     else if (d.Kd == 32) { if (SK == 512) SD_LR(32, lr_cpg(512, 32)); else SD_LR(32, lr_cpg(1024, 32)); }
     else { if (SK == 512) SD_LR(64, lr_cpg(512, 64)); else SD_LR(64, lr_cpg(1024, 64)); }
 #undef SD_LR
-  } else {
-    SD_KD_SWITCH(d.Kd, {
-      const size_t lds = core_lds_floats<KD / 16>() * 4 + (size_t)MR * (UH + 4) * 4;
-      if (!(raise_lds<k_logit<KD>>(lds))) return SD_EARG;
-      k_logit<KD><<<dim3(SK / KD, 1, nt), NTHR, lds, st>>>(dd, w, t);
-    });
   }
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
-bool use_lrows(const sd_rssm_scan& d) { return SD_SCAN_LROWS && (d.SK / d.Kd) % LR_NG == 0; }
 
 }  // namespace
 
@@ -1369,8 +1239,7 @@ extern "C" int sd_rssm_scan_fwd(const sd_rssm_scan* dp, sd_stream stream_) {
   const int B = d.B, D = d.D;
   const int cp_d = cpw_for(D / d.ks_d);
   if (cp_d < 0) return SD_ESHAPE;
-  const bool lrows = use_lrows(d);
-  k_init<<<lrows ? 256 : 64, 256, 0, st>>>(d, lrows ? w.w1t : nullptr);
+  k_init<<<256, 256, 0, st>>>(d, w.w1t);
   SD_LAUNCH_CHECK();
   {  // x0p(0) = h_in[0] . W0^T
     SlabProb p{d.h_in, D, d.W0, D, w.x0s, d.reset, nullptr, 0, 1, 0};
@@ -1380,8 +1249,8 @@ extern "C" int sd_rssm_scan_fwd(const sd_rssm_scan* dp, sd_stream stream_) {
   }
   for (int t = 0; t < d.T; ++t) {
     for (int which = 0; which < 5; ++which) {
-      if (which == 0 && lrows && t > 0) continue;  // x1p[t] slabs written by step t-1's k_logit_rows
-      rc = fwd_phase(d, w, lrows, which, t, st);
+      if (which == 0 && t > 0) continue;  // x1p[t] slabs written by step t-1's k_logit_rows
+      rc = fwd_phase(d, w, which, t, st);
       if (rc) return rc;
     }
   }
@@ -1389,8 +1258,9 @@ extern "C" int sd_rssm_scan_fwd(const sd_rssm_scan* dp, sd_stream stream_) {
 }
 
 // One launch of forward step t's phase `which` exactly as sd_rssm_scan_fwd issues it (same descriptor, workspace and
-// grid): 0 = k_slab (x1p; issued only at t = 0 when k_logit_rows writes the next step's x1p slabs), 1 = k_hid,
-// 2 = k_gate, 3 = k_slab (obs_net_0 deter half + next x0p), 4 = k_logit / k_logit_rows. A measurement aid (bench.py
+// grid): 0 = k_slab (x1p; a run issues it at t = 0 only, k_logit_rows writes the later steps' x1p slabs, but it can be
+// re-issued at any t), 1 = k_hid, 2 = k_gate, 3 = k_slab (obs_net_0 deter half + next x0p), 4 = k_logit_rows. A
+// measurement aid (bench.py
 // times the scan's phases with it, after a full sd_rssm_scan_fwd on the same descriptor); only t = T - 1 rewrites
 // exactly the values the run wrote (the workspace slabs hold the last step's partials).
 extern "C" int sd_rssm_scan_step_kernel(const sd_rssm_scan* dp, int which, int t, sd_stream stream_) {
@@ -1398,7 +1268,7 @@ extern "C" int sd_rssm_scan_step_kernel(const sd_rssm_scan* dp, int which, int t
   if (rc) return rc;
   const sd_rssm_scan& d = *dp;
   if (t < 0 || t >= d.T || which < 0 || which > 4) return SD_EARG;
-  return fwd_phase(d, work_layout(d, d.work), use_lrows(d), which, t, (hipStream_t)stream_);
+  return fwd_phase(d, work_layout(d, d.work), which, t, (hipStream_t)stream_);
 }
 
 extern "C" int sd_rssm_scan_bwd(const sd_rssm_scan* dp, sd_stream stream_) {
@@ -1415,35 +1285,33 @@ extern "C" int sd_rssm_scan_bwd(const sd_rssm_scan* dp, sd_stream stream_) {
   const size_t core1 = core_lds_floats<1>() * 4;
   const size_t lds_dl = core1 + (size_t)MR * (SK + 4) * 4;
   const size_t lds_dgru = core1 + (size_t)MR * (UH + 4) * 4;
-  const int kspan = (d.G / kx_of(d.G)) * Dg;  // k_dhp's longest K span (P0)
-  const size_t lds_dhp = core1 + (size_t)MR * (kspan + 4) * 4;
+  const size_t lds_dhp = core1 + (size_t)MR * (Dg + 4) * 4;  // k_dhp's K span is one block on both problems
   // carry of the step after T-1 is zero. A kernel, not hipMemsetAsync: in a captured HIP graph the memset node was
   // observed not to be ordered before the first k_dgru (garbage carry in replays)
   k_zero<<<sd_cdiv(B * D, 256), 256, 0, st>>>(w.ch, (long)B * D);
   SD_LAUNCH_CHECK();
-  constexpr int DLC = SD_SCAN_DLCW, DGC = SD_SCAN_DGCW, DHC = SD_SCAN_DHCW;
-  const int NX = (3 * UH / 16) * kx_of(d.G);
+  const int NX = (3 * UH / 16) * d.G;  // k_dhp's P0 workgroups: one d_xcat slab per block
   SD_KD_SWITCH(d.Kd, k_sbwd_last<KD><<<(int)(((long)B * SK + 255) / 256), 256, 0, st>>>(d));
   SD_LAUNCH_CHECK();
   for (int t = d.T - 1; t >= 0; --t) {
     d.trace_slot = (d.T + t) * 8;
     if (SK == 512) {
-      if (!(raise_lds<k_dlogit<4, 4, DLC>>(lds_dl))) return SD_EARG;
-      k_dlogit<4, 4, DLC><<<dim3(UH / DLC, 1, nt), NTHR, lds_dl, st>>>(d, w, t);
+      if (!(raise_lds<k_dlogit<4, 4>>(lds_dl))) return SD_EARG;
+      k_dlogit<4, 4><<<dim3(UH / 16, 1, nt), NTHR, lds_dl, st>>>(d, w, t);
     } else {
-      if (!(raise_lds<k_dlogit<8, 8, DLC>>(lds_dl))) return SD_EARG;
-      k_dlogit<8, 8, DLC><<<dim3(UH / DLC, 1, nt), NTHR, lds_dl, st>>>(d, w, t);
+      if (!(raise_lds<k_dlogit<8, 8>>(lds_dl))) return SD_EARG;
+      k_dlogit<8, 8><<<dim3(UH / 16, 1, nt), NTHR, lds_dl, st>>>(d, w, t);
     }
     SD_LAUNCH_CHECK();
     d.trace_slot = (d.T + t) * 8 + 1;
-    k_dgru<DGC><<<dim3(D / DGC, 1, nt), NTHR, lds_dgru, st>>>(d, w, t);
+    k_dgru<<<dim3(D / 16, 1, nt), NTHR, lds_dgru, st>>>(d, w, t);
     SD_LAUNCH_CHECK();
     d.trace_slot = (d.T + t) * 8 + 2;
-    SD_CPW_SWITCH(cp_g3, k_dhh<CP, DHC><<<dim3(D / DHC, 1, nt), NTHR, core1, st>>>(d, w, t));
+    SD_CPW_SWITCH(cp_g3, k_dhh<CP><<<dim3(D / 16, 1, nt), NTHR, core1, st>>>(d, w, t));
     SD_LAUNCH_CHECK();
     d.trace_slot = (d.T + t) * 8 + 3;
-    SD_CPW_SWITCH(kspan / 128, if (!(raise_lds<k_dhp<CP, CP, DHC>>(lds_dhp))) return SD_EARG;
-                  k_dhp<CP, CP, DHC><<<dim3(NX + D / 16, 1, nt), NTHR, lds_dhp, st>>>(d, w, t));
+    SD_CPW_SWITCH(Dg / 128, if (!(raise_lds<k_dhp<CP, CP>>(lds_dhp))) return SD_EARG;
+                  k_dhp<CP, CP><<<dim3(NX + D / 16, 1, nt), NTHR, lds_dhp, st>>>(d, w, t));
     SD_LAUNCH_CHECK();
     d.trace_slot = (d.T + t) * 8 + 4;
     if (t > 0) {  // k_carry builds d_x0p / d_x1p itself (the k_dx01 work in its prologue)

@@ -33,12 +33,8 @@ FUSED_SCAN = os.environ.get("SDREAMER_FUSED_SCAN", "1") != "0"
 # debugging aid: fill the fused backward's scratch tensors with NaN so any element read before it is written shows
 _POISON = os.environ.get("SDREAMER_DEBUG_POISON", "0") != "0"
 # rows per workgroup tile of the fused scan (csrc/scan.hip row_tile): every B rows run as ceil(B / tile) tiles in the
-# same launches; 0 = the 16-row MFMA tile
-SCAN_ROW_TILE = int(os.environ.get("SDREAMER_SCAN_ROWTILE", "0"))
-# per direction (forward / backward launches), overriding SCAN_ROW_TILE when set
-SCAN_ROW_TILE_FWD = int(os.environ.get("SDREAMER_SCAN_ROWTILE_FWD", "-1"))
-SCAN_ROW_TILE_BWD = int(os.environ.get("SDREAMER_SCAN_ROWTILE_BWD", "-1"))
-SCAN_KSD = int(os.environ.get("SDREAMER_SCAN_KSD", "8"))
+# same launches; 0 = the 16-row MFMA tile (tests and tools/scan_trace.py set smaller tiles)
+SCAN_ROW_TILE = 0
 SCAN_TRACE = None  # uint64 device tensor: per-launch / per-workgroup phase timestamps (tools/scan_trace.py)
 
 
@@ -51,15 +47,12 @@ def _fused_scan_ok(rssm, B):
         D % 64 == 0
 
 
-def _scan_desc(rssm, P, B, T, seed, row_offset, rt, x2, eproj, work, stream_id=STREAM_OBS, bwd=False):
+def _scan_desc(rssm, P, B, T, seed, row_offset, rt, x2, eproj, work, stream_id=STREAM_OBS):
     d = nat.ScanDesc()
     D, U, SK, Kd, G = rssm._deter, rssm._hidden, rssm.flat_stoch, rssm._discrete, rssm._blocks
     d.B, d.T, d.D, d.U, d.SK, d.Kd, d.G = B, T, D, U, SK, Kd, G
-    # K splits of the D-wide / SK-wide step GEMMs (slabs summed by the consumer): 8 D-wide slabs = 2 x the k_slab
-    # workgroups of 4, each staging half the weight and deter bytes
-    d.ks_d, d.ks_s = (SCAN_KSD if D % (16 * SCAN_KSD) == 0 else 4), 2
-    side = SCAN_ROW_TILE_BWD if bwd else SCAN_ROW_TILE_FWD
-    d.row_tile = side if side >= 0 else SCAN_ROW_TILE
+    d.ks_d = 8  # split-K slabs of the D-wide step GEMMs: D is a multiple of 256 on every shape _fused_scan_ok admits
+    d.row_tile = SCAN_ROW_TILE
     if SCAN_TRACE is not None:  # measurement aid (tools/scan_trace.py, a -DSD_SCAN_TRACE build of the library)
         d.trace = SCAN_TRACE.data_ptr()
     d.eps, d.unimix = K.EPS, rssm._unimix_ratio
@@ -325,73 +318,84 @@ class ObserveScan(torch.autograd.Function):
         P = rssm._p()
         B, T, A = action.shape
         E = embed.shape[-1]
-        S, Kd, D, U, G = rssm._stoch, rssm._discrete, rssm._deter, rssm._hidden, rssm._blocks
-        SK, Dg = S * Kd, D // G
-        dev = embed.device
-        f32 = torch.float32
+        D, U = rssm._deter, rssm._hidden
         M = T * B
         fused = _fused_scan_ok(rssm, B)
-        # reset flags: the fused scan reads the batch's (B, T) bytes in place (sd_rssm_scan.reset_bm); the per-op
-        # path walks time-major rows
-        rt = reset.contiguous() if fused else reset.t().contiguous()
-        # ---- hoisted, recurrence-free work over all T*B rows. Fused scan: on the batch-major rows b*T + t, read by
-        # the scan in place (bm_inputs); per-op path: time-major rows. The (M, E) embedding is never transposed
-        # (emb_t: batch-major rows, see _wgrads).
+        # ---- hoisted, recurrence-free work over all T*B rows. Fused scan: on the batch-major rows b*T + t, which the
+        # scan reads in place (bm_inputs), like the batch's (B, T) reset bytes (reset_bm); per-op path: time-major
+        # rows. The (M, E) embedding is never transposed (emb_t: batch-major rows, see _wgrads).
         emb_t = embed.detach().reshape(M, E)
         if fused:
+            rt = reset.contiguous()
             a_n = K.action_norm(K.mask_rows(action.reshape(M, A).contiguous(), reset.reshape(M).contiguous()))
             eproj = K.linear(emb_t, P["Wo"][:, D:], P["bo"])
         else:
+            rt = reset.t().contiguous()
             act_t = action.transpose(0, 1).reshape(M, A).contiguous()
             a_n = K.action_norm(K.mask_rows(act_t, rt.reshape(M)))
             eproj = K.linear(emb_t, P["Wo"][:, D:], P["bo"]).view(B, T, U).transpose(0, 1).reshape(M, U).contiguous()
         x2p = K.linear(a_n, P["W2"], P["b2"])
         x2, r2 = K.rmsnorm_fwd(x2p, P["n2"])
-        # ---- per-step buffers (time-major)
-        s_in = torch.empty(T, B, SK, dtype=f32, device=dev)
-        h_in = torch.empty(T, B, D, dtype=f32, device=dev)
-        x0p = torch.empty(T, B, U, dtype=f32, device=dev)
-        x1p = torch.empty(T, B, U, dtype=f32, device=dev)
-        r0 = torch.empty(T, B, dtype=f32, device=dev)
-        r1 = torch.empty(T, B, dtype=f32, device=dev)
-        xcat = torch.empty(T, B, 3 * U, dtype=f32, device=dev)
-        hp = torch.empty(T, B, D, dtype=f32, device=dev)
-        hh = torch.empty(T, B, D, dtype=f32, device=dev)
-        rh = torch.empty(T, B, dtype=f32, device=dev)
-        gates = torch.empty(T, B, 3 * D, dtype=f32, device=dev)
-        deter = torch.empty(T, B, D, dtype=f32, device=dev)
-        op = eproj.view(T, B, U)  # obs_net_0 pre-norm accumulates the deter half in place
-        oo = torch.empty(T, B, U, dtype=f32, device=dev)
-        ro = torch.empty(T, B, dtype=f32, device=dev)
-        logit = torch.empty(T, B, SK, dtype=f32, device=dev)
+        run = ObserveScan._fwd_fused if fused else ObserveScan._fwd_per_op
+        acts, post = run(rssm, P, B, T, rt, x2, eproj, stoch0, deter0, seed, row_offset, stream_id)
+        ctx.save_for_backward(rt, a_n, x2p, r2, emb_t, *acts)
+        ctx.rssm, ctx.seed, ctx.row_offset, ctx.stream_id = rssm, seed, row_offset, stream_id
+        ctx.set_materialize_grads(False)  # a posterior output without a gradient reaches the backward as None
+        ctx.dims = (B, T, A, E)
+        ctx.fused = fused
         if fused:
-            # the posterior outputs written batch-major by the scan itself (the time-major deter / logit stay the
-            # backward's saved activations); obs_net_0's deter half read in place from the full weight
-            post = (torch.empty(B, T, S, Kd, dtype=f32, device=dev), torch.empty(B, T, D, dtype=f32, device=dev),
-                    torch.empty(B, T, S, Kd, dtype=f32, device=dev))
-            Wo = P["Wo"]
-            d = _scan_desc(rssm, P, B, T, seed, row_offset, rt, x2, eproj, None, stream_id)
-            d.bm_inputs, d.ld_wod = 1, Wo.stride(0)
-            work = torch.empty(_scan_work(d), dtype=f32, device=dev)
-            d.work, d.WoD = work.data_ptr(), Wo.data_ptr()
-            d.stoch0, d.deter0 = stoch0.data_ptr(), deter0.data_ptr()
-            op = torch.empty(T, B, U, dtype=f32, device=dev)  # eproj stays the (embed half + bias) input
-            for k, v in (("s_in", s_in), ("h_in", h_in), ("x0p", x0p), ("x1p", x1p), ("r0", r0), ("r1", r1),
-                         ("xcat", xcat), ("hp", hp), ("hh", hh), ("rh", rh), ("gates", gates), ("deter", deter),
-                         ("op", op), ("oo", oo), ("ro", ro), ("logit", logit), ("post_stoch", post[0]),
-                         ("post_deter", post[1]), ("post_logit", post[2])):
-                setattr(d, k, v.data_ptr())
-            d.stoch = None
-            nat.call("sd_rssm_scan_fwd", ctypes.addressof(d), K.stream())
-            if SCAN_KEEP is not None:  # measurement aid (bench.py): the descriptor and every buffer it points to
-                SCAN_KEEP.update(desc=d, work=work, WoD=Wo, bufs=(s_in, h_in, x0p, x1p, r0, r1, xcat, hp, hh, rh,
-                                                                  gates, deter, op, oo, ro, logit, x2, eproj, rt,
-                                                                  stoch0, deter0) + post, T=T, B=B)
-        else:
-            stoch = torch.empty(T, B, SK, dtype=f32, device=dev)
-            xcat[:, :, 2 * U:] = x2.view(T, B, U)
+            ctx.x2 = x2
+        return post
+
+    @staticmethod
+    def _step_bufs(rssm, B, T, dev, op):
+        """The time-major per-step activations both paths fill and the backward reads, in saved order; `op`
+        (obs_net_0's pre-norm) is the caller's."""
+        D, U, SK = rssm._deter, rssm._hidden, rssm.flat_stoch
+        e = lambda *shape: torch.empty(T, B, *shape, dtype=torch.float32, device=dev)  # noqa: E731
+        s_in, h_in, x0p, x1p, r0, r1, xcat = e(SK), e(D), e(U), e(U), e(), e(), e(3 * U)
+        hp, hh, rh, gates, deter = e(D), e(D), e(), e(3 * D), e(D)
+        oo, ro, logit = e(U), e(), e(SK)
+        return s_in, h_in, x0p, x1p, r0, r1, xcat, hp, hh, rh, gates, deter, op, oo, ro, logit
+
+    @staticmethod
+    def _fwd_fused(rssm, P, B, T, rt, x2, eproj, stoch0, deter0, seed, row_offset, stream_id):
+        """The T steps as one sd_rssm_scan_fwd. The posterior outputs are written batch-major by the scan itself (the
+        time-major deter / logit stay the backward's saved activations; no time-major stoch); obs_net_0's deter half
+        is read in place from the full weight, eproj stays the (embed half + bias) input."""
+        S, Kd, D, U = rssm._stoch, rssm._discrete, rssm._deter, rssm._hidden
+        dev, f32 = x2.device, torch.float32
+        acts = ObserveScan._step_bufs(rssm, B, T, dev, torch.empty(T, B, U, dtype=f32, device=dev))
+        post = (torch.empty(B, T, S, Kd, dtype=f32, device=dev), torch.empty(B, T, D, dtype=f32, device=dev),
+                torch.empty(B, T, S, Kd, dtype=f32, device=dev))
+        Wo = P["Wo"]
+        d = _scan_desc(rssm, P, B, T, seed, row_offset, rt, x2, eproj, None, stream_id)
+        d.bm_inputs, d.ld_wod = 1, Wo.stride(0)
+        work = torch.empty(_scan_work(d), dtype=f32, device=dev)
+        d.work, d.WoD = work.data_ptr(), Wo.data_ptr()
+        d.stoch0, d.deter0 = stoch0.data_ptr(), deter0.data_ptr()
+        names = ("s_in", "h_in", "x0p", "x1p", "r0", "r1", "xcat", "hp", "hh", "rh", "gates", "deter", "op", "oo", "ro",
+                 "logit", "post_stoch", "post_deter", "post_logit")
+        for k, v in zip(names, acts + post):
+            setattr(d, k, v.data_ptr())
+        d.stoch = None
+        nat.call("sd_rssm_scan_fwd", ctypes.addressof(d), K.stream())
+        if SCAN_KEEP is not None:  # measurement aid (bench.py): the descriptor and every buffer it points to
+            SCAN_KEEP.update(desc=d, work=work, WoD=Wo, bufs=acts + (x2, eproj, rt, stoch0, deter0) + post, T=T, B=B)
+        return acts, post
+
+    @staticmethod
+    def _fwd_per_op(rssm, P, B, T, rt, x2, eproj, stoch0, deter0, seed, row_offset, stream_id):
+        """The T steps on the per-op HIP kernels (the fused scan's test oracle, and the path of shapes outside
+        _fused_scan_ok), everything time-major; obs_net_0's pre-norm accumulates the deter half into eproj in place."""
+        S, Kd, D, U, G = rssm._stoch, rssm._discrete, rssm._deter, rssm._hidden, rssm._blocks
+        SK, Dg = S * Kd, D // G
+        acts = ObserveScan._step_bufs(rssm, B, T, x2.device, eproj.view(T, B, U))
+        s_in, h_in, x0p, x1p, r0, r1, xcat, hp, hh, rh, gates, deter, op, oo, ro, logit = acts
+        stoch = torch.empty(T, B, SK, dtype=torch.float32, device=x2.device)
+        xcat[:, :, 2 * U:] = x2.view(T, B, U)
         prev_s, prev_h = stoch0, deter0
-        for t in (range(0) if fused else range(T)):
+        for t in range(T):
             m = rt[t]
             K.mask_rows(prev_s, m, out=s_in[t])
             K.mask_rows(prev_h, m, out=h_in[t])
@@ -411,19 +415,10 @@ class ObserveScan(torch.autograd.Function):
             K.linear(oo[t], P["Wl"], P["bl"], out=logit[t])
             K.onehot_sample(logit[t], Kd, rssm._unimix_ratio, seed, stream_id, t, row_offset * S, out=stoch[t])
             prev_s, prev_h = stoch[t], deter[t]
-        ctx.save_for_backward(rt, a_n, x2p, r2, emb_t, s_in, h_in, x0p, x1p, r0, r1, xcat, hp, hh, rh, gates, deter,
-                              op, oo, ro, logit)
-        ctx.rssm, ctx.seed, ctx.row_offset, ctx.stream_id = rssm, seed, row_offset, stream_id
-        ctx.set_materialize_grads(False)  # a posterior output without a gradient reaches the backward as None
-        ctx.dims = (B, T, A, E)
-        ctx.fused = fused
-        if fused:
-            ctx.x2 = x2
-            return post
         post_stoch = stoch.transpose(0, 1).reshape(B, T, S, Kd).contiguous()
         post_deter = deter.transpose(0, 1).contiguous()
         post_logit = logit.transpose(0, 1).reshape(B, T, S, Kd).contiguous()
-        return post_stoch, post_deter, post_logit
+        return acts, (post_stoch, post_deter, post_logit)
 
     @staticmethod
     def backward(ctx, d_stoch, d_deter, d_logit):
@@ -518,7 +513,7 @@ class ObserveScan(torch.autograd.Function):
         d_gates, d_hh, d_hp, d_xcat = e(T, B, 3 * D), e(T, B, D), e(T, B, D), e(T, B, 3 * U)
         tr = rssm._bwd_tr if rssm._bwd_tr is not None else rssm.scan_bwd_weights()
         x2 = ctx.x2
-        d = _scan_desc(rssm, P, B, T, ctx.seed, ctx.row_offset, rt, x2, x2, None, ctx.stream_id, bwd=True)
+        d = _scan_desc(rssm, P, B, T, ctx.seed, ctx.row_offset, rt, x2, x2, None, ctx.stream_id)
         work = e(_scan_work(d))
         d.work = work.data_ptr()
         for k, v in list(tr.items()) + [("s_in", s_in), ("h_in", h_in), ("x0p", x0p), ("x1p", x1p), ("r0", r0),

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build A/B variants of libsdhip.so with extra -D flags into _var/<name>/libsdhip.so (CPU container), e.g.
-#   tools/ab_variants.sh cp0 "-DSD_CORE_PAIR=0" ng4 "-DSD_LR_NG=4"
+#   tools/ab_variants.sh trace "-DSD_SCAN_TRACE"
+# (the trace build is the only -D variant the sources still have; a new experiment adds its own switch first)
 # then on the GPU box: SDHIP_LIB=_var/<name>/libsdhip.so python tools/imag_bench.py 10
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
