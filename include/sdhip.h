@@ -269,6 +269,15 @@ int sd_conv2d_wgrad_pool_bf16x3_slabs(int Nb, int H, int W, int Ci, int Co, int 
 int sd_conv2d_wgrad_pool_bf16x3(const float* in, const float* dpool, const uint8_t* amax, float* dw_db,
                                 float* workspace, long ws_floats, int Nb, int H, int W, int Ci, int Co, int kh, int kw,
                                 int pad, const sd_wgrad_acc* acc, sd_stream stream);
+/* Input gradient of a pooled ConvEncoder stage from (dpool, argmax) of sd_pool_rms_bwd_compact[_film]:
+ * din (Nb, H, W, Ci) = conv_same(expand(dpool, amax), flipped w), w (Co, kh, kw, Ci) as the forward holds it (not
+ * flipped, not channel-padded), din with the real channel count. The conv gradient is expanded in LDS only. Plain f32
+ * FMAs in a fixed order. Instantiated for the encoders' first stage: Co = 32, Ci = 3, 5x5, pad 2, W = 64, H even;
+ * SD_ESHAPE otherwise (the caller then runs sd_pool_rms_bwd + sd_conv2d_dgrad_* on the channel-padded weight).
+ * _ok: 1 when the shape is taken, else 0 (asked before the caller chooses which max-pool backward to run). */
+int sd_conv2d_dgrad_pool_ok(int H, int W, int Co, int Ci, int kh, int kw, int pad);
+int sd_conv2d_dgrad_pool(const float* dpool, const uint8_t* amax, const float* w, float* din, int Nb, int H, int W,
+                         int Co, int Ci, int kh, int kw, int pad, sd_stream stream);
 /* The same bwd-data as a direct convolution (csrc/conv.hip conv_dgrad3_direct: each workgroup stages its dOut patch
  * once, split to bf16 planes; same products and order per k as sd_conv2d_dgrad_bf16x3, k summed in the same order).
  * wsplit = sd_conv_split_weight(wflip, rows = Co, K = kh*kw*Ci). Instantiated for the 5x5 pad-2 stages of the
@@ -460,6 +469,26 @@ int sd_pad_channels(const float* in, float* out, long pixels, int C, int Cp, flo
  * reads it) and enc = in / 255 - shift zero-padded to Cp channels (the ConvEncoder input, networks.py:224). */
 int sd_u8_image_inputs(const uint8_t* in, float* img, float* enc, long pixels, int C, int Cp, float shift,
                        sd_stream stream);
+/* Adversarial image patch (csrc/attack.hip, sdreamer/attack.py). Images are NHWC (Nb, H, W, C); patch (ph, pw, C) f32
+ * in [0, 1]; offsets (Nb, 2) int32 = each image's (row, column) of the patch's top-left corner, any sign: the window
+ * is clipped at the image borders.
+ * apply: in = uint8 bytes (in_u8 != 0, read as in / 255) or f32 in [0, 1]; img (nullable) = the composited f32 image,
+ *   enc (nullable) = img - shift zero-padded to Cp channels (as sd_u8_image_inputs writes them).
+ * grad: dpatch[e] = the sum of dimg at patch element e's position over the images whose clipped window contains it:
+ *   chunks of SD_PATCH_CHUNK images summed in image order into part (>= ceil(Nb / SD_PATCH_CHUNK) * ph*pw*C floats),
+ *   then the chunks in order. patch != NULL: + w_tv * d TV / d patch with TV = sum |horizontal differences| + sum
+ *   |vertical differences| of the patch (sign(0) = 0), and tv[0] = TV (tv nullable).
+ * step: one torch.optim.Adam step (no weight decay / amsgrad) on the n patch elements with the moments m, v and the
+ *   step counter step[0] (int32, advanced by the launch) on the device, then the clamp to [0, 1]; base != NULL: then
+ *   the clamp to [base - linf_eps, base + linf_eps]. One launch, no host synchronisation. */
+#define SD_PATCH_CHUNK 32
+int sd_patch_apply(const void* in, int in_u8, const float* patch, const int* offsets, float* img, float* enc, int Nb,
+                   int H, int W, int C, int Cp, int ph, int pw, float shift, sd_stream stream);
+int sd_patch_grad(const float* dimg, const int* offsets, float* dpatch, float* part, long part_floats,
+                  const float* patch, float w_tv, float* tv, int Nb, int H, int W, int C, int ph, int pw,
+                  sd_stream stream);
+int sd_patch_step(float* patch, const float* dpatch, float* m, float* v, int* step, const float* base, float lr,
+                  float beta1, float beta2, float adam_eps, float linf_eps, long n, sd_stream stream);
 /* symlog (distributions.py:8-9) for MLP-encoder inputs (networks.py:333-334) */
 int sd_symlog(const float* x, float* y, long n, sd_stream stream);
 int sd_fill_gumbel(float* out, long n, uint64_t seed, int stream_id, int step, long offset, sd_stream stream);

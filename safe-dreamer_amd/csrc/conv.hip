@@ -2462,3 +2462,106 @@ extern "C" int sd_conv2d_wgrad_bf16x3(const float* in, const float* dout, float*
   if (!direct3_plan(Nb, Hs, Ws, Ci, Co, kh, kw, 0, pl) || !al16(in) || !al16(dout)) return SD_ESHAPE;
   return wgrad3_direct(in, dout, dw_db, workspace, ws_floats, Nb, Hs, Ws, Ci, Co, kh, kw, pad, pl, s, acc);
 }
+
+// ---------------------------------------------------------------- first-stage input gradient from the pooled gradient
+// dIn (Nb, H, 64, 3) = conv_same(expand(dpool, amax), flipped W) for the encoder's first stage (32 -> 3 channels, 5x5,
+// pad 2). A workgroup owns a 16-row x 64-column tile of one image; the conv gradient of that tile (+ 2 halo rows /
+// columns) exists only in LDS, 8 output channels at a time: each of the 10 x 32 pooled pixels of the slab writes its
+// gradient at the argmax position of its 2x2 window and zeros at the other three. A thread owns one column and four
+// rows (12 f32 accumulators); per (kx, 4 channels) it reads 8 rows as float4 (column stride 12 floats: the 16 lanes of
+// a ds_read_b128 phase hit 16 distinct bank quads) and issues 240 FMAs whose weight operand is wave-uniform (scalar
+// loads of w). Plain f32 FMAs in a fixed (channel chunk, kx, channel, row, ky) order: no atomics, no split products.
+namespace {
+constexpr int DP_CO = 32, DP_KS = 5, DP_W = 64, DP_CI = 3, DP_TH = 16, DP_R = 4, DP_CC = 8, DP_CS = 12;
+constexpr int DP_LW = DP_W + DP_KS - 1, DP_LR = DP_TH + DP_KS - 1, DP_RS = DP_LW * DP_CS;
+
+__global__ __launch_bounds__(256, 2) void conv_dgrad_pool_k(const float* __restrict__ dpool,
+                                                           const uint8_t* __restrict__ amax,
+                                                           const float* __restrict__ w, float* __restrict__ din,
+                                                           int H) {
+  __shared__ __attribute__((aligned(16))) float tile[DP_LR * DP_RS];
+  const int tid = threadIdx.x;
+  const int tiles = (H + DP_TH - 1) / DP_TH;
+  const int n = blockIdx.x / tiles, y0 = (blockIdx.x % tiles) * DP_TH;
+  const int Ho = H / 2, Wo = DP_W / 2;
+  // halo columns (outside the image) stay zero for every channel chunk
+  for (int i = tid; i < DP_LR * 4 * DP_CC; i += 256) {
+    const int c = i % DP_CC, h = (i / DP_CC) % 4, r = i / (4 * DP_CC);
+    tile[r * DP_RS + (h < 2 ? h : DP_W + h) * DP_CS + c] = 0.f;
+  }
+  const int sx = tid / DP_CC, sc = tid % DP_CC;  // staging: pooled column, channel of the chunk
+  const int x = tid % DP_W, l0 = (tid / DP_W) * DP_R;
+  float acc[DP_R][DP_CI];
+#pragma unroll
+  for (int r = 0; r < DP_R; ++r)
+#pragma unroll
+    for (int ci = 0; ci < DP_CI; ++ci) acc[r][ci] = 0.f;
+
+  for (int c0 = 0; c0 < DP_CO; c0 += DP_CC) {
+    if (c0) __syncthreads();
+    // pooled rows y0/2 - 1 .. y0/2 + 8 -> conv-gradient rows y0 - 2 .. y0 + 17 (tile rows 0 .. 19)
+    for (int i = 0; i < DP_LR / 2; ++i) {
+      const int pr = y0 / 2 - 1 + i;
+      float dp = 0.f;
+      int q = 0;
+      if (pr >= 0 && pr < Ho) {
+        const long o = (((long)n * Ho + pr) * Wo + sx) * DP_CO + c0 + sc;
+        dp = dpool[o];
+        q = amax[o];
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        tile[(2 * i + (a >> 1)) * DP_RS + (2 + 2 * sx + (a & 1)) * DP_CS + sc] = q == a ? dp : 0.f;
+    }
+    __syncthreads();
+    // one (kx, 4 channels) step per iteration, not unrolled: its 60 weights fit the scalar registers (unrolling the
+    // ten steps makes hipcc hoist all 600 scalar loads and spill ~670 SGPRs)
+#pragma unroll 1
+    for (int kx = 0; kx < DP_KS; ++kx) {
+#pragma unroll 1
+      for (int c4 = 0; c4 < DP_CC; c4 += 4) {
+        f32x4 v[DP_R + DP_KS - 1];
+#pragma unroll
+        for (int j = 0; j < DP_R + DP_KS - 1; ++j)
+          v[j] = *reinterpret_cast<const f32x4*>(&tile[(l0 + j) * DP_RS + (x + kx) * DP_CS + c4]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          // dIn[y][x] += dConv[y + ky - 2][x + kx - 2][co] * W[co][4 - ky][4 - kx]
+          const float* wc = w + ((long)(c0 + c4 + c) * DP_KS * DP_KS + (DP_KS - 1 - kx)) * DP_CI;
+#pragma unroll
+          for (int r = 0; r < DP_R; ++r)
+#pragma unroll
+            for (int ky = 0; ky < DP_KS; ++ky)
+#pragma unroll
+              for (int ci = 0; ci < DP_CI; ++ci)
+                acc[r][ci] = fmaf(v[r + ky][c], wc[(DP_KS - 1 - ky) * DP_KS * DP_CI + ci], acc[r][ci]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < DP_R; ++r) {
+    const int y = y0 + l0 + r;
+    if (y < H) {
+      float* o = din + (((long)n * H + y) * DP_W + x) * DP_CI;
+#pragma unroll
+      for (int ci = 0; ci < DP_CI; ++ci) o[ci] = acc[r][ci];
+    }
+  }
+}
+}  // namespace
+
+extern "C" int sd_conv2d_dgrad_pool_ok(int H, int W, int Co, int Ci, int kh, int kw, int pad) {
+  return Co == DP_CO && Ci == DP_CI && kh == DP_KS && kw == DP_KS && pad == DP_KS / 2 && W == DP_W && H >= 2 &&
+         H % 2 == 0;
+}
+extern "C" int sd_conv2d_dgrad_pool(const float* dpool, const uint8_t* amax, const float* w, float* din, int Nb, int H,
+                                    int W, int Co, int Ci, int kh, int kw, int pad, sd_stream stream_) {
+  if (!sd_conv2d_dgrad_pool_ok(H, W, Co, Ci, kh, kw, pad) || (long)Nb * sd_cdiv(H, DP_TH) > 0x7fffffffL)
+    return SD_ESHAPE;
+  if (Nb <= 0) return SD_OK;
+  if (!dpool || !amax || !w || !din) return SD_EARG;
+  conv_dgrad_pool_k<<<Nb * sd_cdiv(H, DP_TH), 256, 0, (hipStream_t)stream_>>>(dpool, amax, w, din, H);
+  SD_LAUNCH_CHECK();
+  return SD_OK;
+}

@@ -395,6 +395,64 @@ class Dreamer(nn.Module):
             action = self._sample_action(logits, seed, step, 0, STREAM_POLICY_ACT)
         return action, {"stoch": stoch, "deter": deter, "prev_action": action}
 
+    def _posterior_text_ctx(self, B, text_index=None):
+        """(B, dim) context of text `text_index` (default: the update schedule's current text, the first one before
+        any update) in a buffer of its own: neither the update's persistent buffer nor its schedule is touched."""
+        enc = self.encoder
+        enc._need_features()
+        idx = text_index if text_index is not None else (enc._text_index if enc._text_index is not None else 0)
+        out = torch.empty(B, enc.text_context_encoder.text_context_dim, dtype=torch.float32, device=self.device)
+        return enc.text_context_encoder(enc._feats[int(idx)].to(self.device), out=out)
+
+    def posterior(self, data, initial, seed=0, with_grad=False, text_ctx=None):
+        """Encoder -> posterior scan of a batch (dreamer.py:453-470): data a dict of (B, T, *) device tensors (image
+        uint8, or float in [0, 1]), initial ((B, S, K), (B, D)) -> (post_stoch, post_deter, post_logit), the
+        posterior noise from `seed` as in the update. Eager, on the current stream.
+
+        with_grad: data["image"] is f32 in [0, 1] and requires grad, and the autograd graph of the result reaches it
+        (d loss / d observation). No parameter gradient the optimizer would see is written: the backward of this
+        graph routes its parameter-gradient accumulations to scratch buffers (ops.GradSinkFn), so the gradient arena
+        and `_grads_clean` stay as they are. Wrap a backward that also runs other parameterised layers (an actor on
+        the posterior features, say) in ops.grad_sink_scope(), as observation_grad does.
+
+        text_ctx (multimodal encoder): the (B, dim) text context; default the update schedule's current text, computed
+        into a buffer of its own (the schedule does not advance)."""
+        if self.world > 1:
+            raise NotImplementedError("Dreamer.posterior runs on one GPU (the data-parallel update owns the others)")
+        data = {k: v for k, v in data.items() if k != "__enc_image"}
+        B = data["action"].shape[0]
+        if self._mm and text_ctx is None:
+            text_ctx = self._posterior_text_ctx(B)
+        if with_grad:
+            img = data.get("image")
+            if img is None or img.dtype != torch.float32 or not img.requires_grad:
+                raise ValueError("posterior(with_grad=True) needs data['image'] as float32 in [0, 1] with "
+                                 "requires_grad=True")
+            self.rssm._bwd_tr = None  # nothing prepared for another backward may be reused by this one
+            K.clear_flip_cache()
+        with torch.set_grad_enabled(bool(with_grad)):
+            if not with_grad:
+                data = self.preprocess(data)
+            if self._mm:
+                out = self.encoder(data, return_both=True, reuse_text_context=text_ctx)
+                enc_out = out[1] if isinstance(out, tuple) else out
+            else:
+                enc_out = self.encoder(data)
+            post = self.rssm.observe(enc_out, data["action"], initial, data["is_first"], seed=seed)
+            return ops.GradSinkFn.apply(*post) if with_grad else post
+
+    def observation_grad(self, data, initial, loss_fn, seed=0, text_ctx=None):
+        """d loss / d observation: loss_fn(post_stoch, post_deter, post_logit) -> scalar, on the posterior of
+        data["image"] (f32 in [0, 1], or uint8) -> (loss, d_image (B, T, H, W, C)). The input tensors are left alone
+        (the gradient is taken on a detached copy of the image); no parameter gradient is written."""
+        img = data["image"]
+        img = (K.u8_to_f32(img.contiguous()) if img.dtype == torch.uint8 else img.detach()).requires_grad_(True)
+        with ops.grad_sink_scope():
+            post = self.posterior({**data, "image": img}, initial, seed=seed, with_grad=True, text_ctx=text_ctx)
+            loss = loss_fn(*post)
+            (d_image,) = torch.autograd.grad(loss, img)
+        return loss.detach(), d_image
+
     @torch.no_grad()
     def video_pred(self, data, initial, seed=0):
         """dreamer.py:366-400 (rep_loss == "dreamer" only): posterior over the first 5 steps, then open-loop

@@ -676,6 +676,105 @@ def conv2d_wgrad_pool(x, dpool, amax, kh, kw, pad=None, acc=None):
     return None if acc is not None else out
 
 
+def conv2d_dgrad_pool_takes(H, W, Co, Ci, kh, kw, pad=None):
+    """True when conv2d_dgrad_pool (sd_conv2d_dgrad_pool) handles this stage's shape."""
+    pad = (kh - 1) // 2 if pad is None else pad
+    return nat.fns["sd_conv2d_dgrad_pool_ok"](H, W, Co, Ci, kh, kw, pad) > 0
+
+
+DGRAD_POOL_CALLS = 0  # calls of conv2d_dgrad_pool so far (tests: the update path never makes one)
+
+
+def conv2d_dgrad_pool(dpool, amax, w, pad=None):
+    """Input gradient of a pooled stage from the max-pool backward's pooled-resolution gradient dpool (Nb, H/2, W/2,
+    Co) and the forward's argmax amax (uint8, same shape): conv_same(expand(dpool, amax), flipped w) -> (Nb, H, W, Ci)
+    with w (Co, kh, kw, Ci) as the forward holds it (real channel count). The expanded gradient exists in LDS only;
+    plain f32 FMAs in a fixed order. None when the shape is outside the kernel (the encoder's first stage: 32 -> 3
+    channels, 5x5, W = 64): the caller then runs pool_rms_bwd + conv2d_dgrad on the channel-padded weight."""
+    global DGRAD_POOL_CALLS
+    DGRAD_POOL_CALLS += 1
+    Nb, Ho, Wo, Co = dpool.shape
+    _, kh, kw, Ci = w.shape
+    _chk(dpool, amax, w)
+    if amax.shape != dpool.shape or amax.dtype != torch.uint8 or w.shape[0] != Co:
+        raise ValueError(f"conv2d_dgrad_pool: dpool {tuple(dpool.shape)}, amax {tuple(amax.shape)} {amax.dtype}, "
+                         f"w {tuple(w.shape)}")
+    pad = (kh - 1) // 2 if pad is None else pad
+    H, W = 2 * Ho, 2 * Wo
+    if not conv2d_dgrad_pool_takes(H, W, Co, Ci, kh, kw, pad):
+        return None
+    din = torch.empty(Nb, H, W, Ci, dtype=torch.float32, device=dpool.device)
+    if not nat.call_shaped("sd_conv2d_dgrad_pool", p(_c(dpool)), p(_c(amax)), p(_c(w)), p(din), Nb, H, W, Co, Ci, kh,
+                           kw, pad, stream()):
+        return None
+    return din
+
+
+# ------------------------------------------------------------------------------------------------- adversarial patch
+_PATCH_CHUNK = nat._define(nat.HEADER, "SD_PATCH_CHUNK")
+
+
+def _patch_args(images, patch, offsets):
+    _chk(images, patch, offsets)
+    Nb, H, W, C = images.shape
+    ph, pw, pc = patch.shape
+    if pc != C or patch.dtype != torch.float32 or offsets.shape != (Nb, 2) or offsets.dtype != torch.int32:
+        raise ValueError(f"patch {tuple(patch.shape)} {patch.dtype} / offsets {tuple(offsets.shape)} {offsets.dtype} "
+                         f"for images {tuple(images.shape)}")
+    return Nb, H, W, C, ph, pw
+
+
+def patch_apply(images, patch, offsets, Cp=None, shift=0.5, need_f32=True):
+    """images (Nb, H, W, C) uint8 or f32 in [0, 1], patch (ph, pw, C) f32, offsets (Nb, 2) int32 (row, column of the
+    patch's top-left corner per image; the window is clipped at the borders) -> (composited f32 image or None,
+    encoder input image - shift zero-padded to Cp channels), one launch (sd_patch_apply)."""
+    Nb, H, W, C, ph, pw = _patch_args(images, patch, offsets)
+    if images.dtype not in (torch.uint8, torch.float32):
+        raise TypeError("patch_apply takes uint8 or float32 images")
+    Cp = (C + 3) // 4 * 4 if Cp is None else Cp
+    f = torch.empty(images.shape, dtype=torch.float32, device=images.device) if need_f32 else None
+    enc = torch.empty(Nb, H, W, Cp, dtype=torch.float32, device=images.device)
+    nat.call("sd_patch_apply", p(_c(images)), int(images.dtype == torch.uint8), p(_c(patch)), p(_c(offsets)), p(f),
+             p(enc), Nb, H, W, C, Cp, ph, pw, float(shift), stream())
+    return f, enc
+
+
+def patch_grad(d_image, offsets, patch_hw, patch=None, w_tv=0.0):
+    """The adjoint of patch_apply in the patch: d_patch (ph, pw, C), each element's sum of d_image over the images
+    whose clipped window contains it (fixed-order two-stage sum: bit-identical on repetition). patch given: adds
+    w_tv * the gradient of the anisotropic total variation and returns (d_patch, tv (1,)), else (d_patch, None)."""
+    Nb, H, W, C = d_image.shape
+    ph, pw = patch_hw
+    _chk(d_image, offsets, patch)
+    if offsets.shape != (Nb, 2) or offsets.dtype != torch.int32 or d_image.dtype != torch.float32:
+        raise ValueError("patch_grad: d_image (Nb, H, W, C) f32, offsets (Nb, 2) int32")
+    if patch is not None and (tuple(patch.shape) != (ph, pw, C) or patch.dtype != torch.float32):
+        raise ValueError("patch_grad: patch must be (ph, pw, C) f32")
+    dev = d_image.device
+    dpatch = torch.empty(ph, pw, C, dtype=torch.float32, device=dev)
+    part = torch.empty(-(-Nb // _PATCH_CHUNK) * ph * pw * C, dtype=torch.float32, device=dev)
+    tv = torch.empty(1, dtype=torch.float32, device=dev) if patch is not None else None
+    nat.call("sd_patch_grad", p(_c(d_image)), p(_c(offsets)), p(dpatch), p(part), part.numel(),
+             p(_c(patch) if patch is not None else None), float(w_tv), p(tv), Nb, H, W, C, ph, pw, stream())
+    return dpatch, tv
+
+
+def patch_step(patch, d_patch, m, v, step, lr, base=None, eps=None, betas=(0.9, 0.999), adam_eps=1e-8):
+    """One torch.optim.Adam step on `patch` in place (moments m, v and the int32 counter step (1,) on the device),
+    then the clamp to [0, 1] and, with eps, to [base - eps, base + eps]; one launch, no host sync."""
+    _chk(patch, d_patch, m, v, step, base)
+    n = patch.numel()
+    if not (d_patch.numel() == m.numel() == v.numel() == n) or step.dtype != torch.int32:
+        raise ValueError("patch_step: patch, gradient and moments must match; step is int32")
+    if (eps is None) != (base is None) and eps is not None:
+        raise ValueError("patch_step: eps needs the base patch")
+    use = eps is not None
+    nat.call("sd_patch_step", p(_c(patch)), p(_c(d_patch)), p(_c(m)), p(_c(v)), p(step),
+             p(_c(base)) if use else 0, float(lr), float(betas[0]), float(betas[1]), float(adam_eps),
+             float(eps) if use else 0.0, n, stream())
+    return patch
+
+
 _FLIP = {}  # weight data_ptr -> flipped weight, built ahead of the backward (set_flip_cache)
 _SPLIT = {}  # weight data_ptr -> split-bf16 image of the flipped weight (sd_conv_split_weight), same lifetime
 # SDREAMER_CONV6: the encoder stages' forward on the fp32-accurate three-way split-bf16 direct kernel

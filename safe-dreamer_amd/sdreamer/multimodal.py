@@ -92,13 +92,14 @@ class FiLMConvEncoder(nn.Module):
     def dgrad_weights(self):
         return [self.convs[i].weight for i in range(1, len(self.depths))]
 
-    def forward(self, x, ctx, split=None):
-        """ctx (B, ctx_dim), one row per x.shape[0] // B consecutive images. split: see ConvEncoder.forward."""
+    def forward(self, x, ctx, split=None, pad_shift=None):
+        """ctx (B, ctx_dim), one row per x.shape[0] // B consecutive images. split, pad_shift: see
+        ConvEncoder.forward."""
         n = len(self.depths)
         for i in range(n):
             gamma, beta = self.films[i](ctx)
             x = ops.FilmConvPoolNormFn.apply(x, self.convs[i].weight, self.convs[i].bias, self.norms[i].weight, gamma,
-                                             beta, i == n - 1)
+                                             beta, i == n - 1, pad_shift if i == 0 else None)
             if i == 0 and n > 1 and split is not None and x.requires_grad:
                 leaf = x.detach().requires_grad_(True)
                 split.append((x, leaf))
@@ -305,19 +306,24 @@ class _TextConditioned(nn.Module):
                     torch.linalg.vector_norm(proj[2].weight)}
 
     def _images(self, obs):
-        """obs['image'] (B, T, H, W, C) or (B, H, W, C) float in [0, 1] -> (x (N, H, W, Cp) shifted by -0.5, B, T)"""
+        """obs['image'] (B, T, H, W, C) or (B, H, W, C) float in [0, 1] -> (x (N, H, W, Cp) shifted by -0.5, B, T,
+        has_time, pad_shift). pad_shift 0.5: x is the raw image, whose gradient is wanted; the first stage shifts and
+        pads it itself (ConvEncoder.forward)."""
         pre = obs.get("__enc_image")  # formed by Dreamer.preprocess(enc_input=True) from the uint8 bytes
         img = pre if pre is not None else obs["image"]
         has_time = img.dim() == 5
         B, T = (img.shape[0], img.shape[1]) if has_time else (img.shape[0], 1)
         x = img.reshape(-1, *img.shape[-3:]).contiguous()
+        pad_shift = None
         if pre is not None:
             pass
+        elif x.shape[-1] % 4 and x.requires_grad and torch.is_grad_enabled():
+            pad_shift = 0.5
         elif x.shape[-1] % 4:
             x = K.pad_channels(x, (x.shape[-1] + 3) // 4 * 4, 0.5)
         else:
             x = x - 0.5
-        return x, B, T, has_time
+        return x, B, T, has_time, pad_shift
 
     def _finish(self, visual, ctx, B, T, has_time, return_both):
         shape = (B, T, -1) if has_time else (B, -1)
@@ -349,9 +355,9 @@ class MultimodalEncoder(_TextConditioned):
         return self.visual_encoder.dgrad_weights()
 
     def forward(self, obs, return_both=True, reuse_text_context=None, split=None):
-        x, B, T, has_time = self._images(obs)
+        x, B, T, has_time, pad_shift = self._images(obs)
         ctx = reuse_text_context if reuse_text_context is not None else self.text_context(B, x.device)
-        visual = self.visual_encoder(x, ctx, split)
+        visual = self.visual_encoder(x, ctx, split, pad_shift)
         return self._finish(visual, ctx, B, T, has_time, return_both)
 
 
@@ -373,8 +379,8 @@ class GateOnlyEncoder(_TextConditioned):
         return self.conv_encoder.dgrad_weights()
 
     def forward(self, obs, return_both=True, reuse_text_context=None, split=None):
-        x, B, T, has_time = self._images(obs)
-        visual = self.conv_encoder(x, split)
+        x, B, T, has_time, pad_shift = self._images(obs)
+        visual = self.conv_encoder(x, split, pad_shift)
         ctx = None
         if return_both and self._use_text_gate:
             ctx = reuse_text_context if reuse_text_context is not None else self.text_context(B, x.device)

@@ -330,14 +330,17 @@ class ConvEncoder(nn.Module):
         """conv weights whose input gradient the backward computes (every stage but the first)"""
         return [self.layers[4 * i].weight for i in range(1, len(self.depths))]
 
-    def forward(self, obs, split=None):
+    def forward(self, obs, split=None, pad_shift=None):
         """split (a list): the first stage's output is continued as a detached leaf and (output, leaf) appended, so
-        the backward runs as two calls (stages 2.. down to the leaf, then the first stage)."""
+        the backward runs as two calls (stages 2.. down to the leaf, then the first stage). pad_shift: obs is the raw
+        image whose gradient is wanted; the first stage forms obs - pad_shift, channel-padded, itself (ops._stage_input)
+        and returns the gradient in the image's own shape."""
         x = obs
         n = len(self.depths)
         for i in range(n):
             conv, norm = self.layers[4 * i], self.layers[4 * i + 2]
-            x = ops.ConvPoolNormFn.apply(x, conv.weight, conv.bias, norm.weight, i == n - 1)
+            x = ops.ConvPoolNormFn.apply(x, conv.weight, conv.bias, norm.weight, i == n - 1,
+                                         pad_shift if i == 0 else None)
             if i == 0 and n > 1 and split is not None and x.requires_grad:
                 leaf = x.detach().requires_grad_(True)
                 split.append((x, leaf))
@@ -386,13 +389,16 @@ class MultiEncoder(nn.Module):
                     else obs[next(iter(self.cnn_shapes))])
                 BT = img.shape[:-3]
                 x = img.reshape(-1, *img.shape[-3:])
+                pad_shift = None
                 if pre is not None:
                     pass
+                elif x.shape[-1] % 4 and x.requires_grad and torch.is_grad_enabled():
+                    pad_shift = 0.5  # the image's gradient is wanted: the first stage pads (and un-pads) itself
                 elif x.shape[-1] % 4:  # obs - 0.5 (networks.py:224), zero-padded to a float4 channel multiple
                     x = K.pad_channels(x.contiguous(), (x.shape[-1] + 3) // 4 * 4, 0.5)
                 else:
                     x = x - 0.5  # ConvEncoder.forward, networks.py:224
-                outs.append(enc(x.contiguous(), split).reshape(*BT, -1))
+                outs.append(enc(x.contiguous(), split, pad_shift).reshape(*BT, -1))
             else:
                 x = torch.cat([obs[k] for k in self.mlp_shapes], -1)
                 outs.append(enc(x))

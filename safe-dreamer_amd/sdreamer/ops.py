@@ -17,10 +17,55 @@ from . import kernels as k
 FUSED_POOL = os.environ.get("SDREAMER_FUSED_POOL", "1") != "0"
 
 
+_GRAD_SINK = None  # a dict while a backward's parameter gradients are routed to scratch buffers (grad_sink_scope)
+
+
 def grad_buf(param):
+    if _GRAD_SINK is not None:  # id(param) -> scratch, dropped when the backward ends: param.grad is never touched
+        buf = _GRAD_SINK.get(id(param))
+        if buf is None:
+            buf = _GRAD_SINK[id(param)] = torch.zeros_like(param)
+        return buf
     if param.grad is None:
         param.grad = torch.zeros_like(param)
     return param.grad
+
+
+def close_grad_sink():
+    global _GRAD_SINK
+    _GRAD_SINK = None
+
+
+class grad_sink_scope:
+    """Within this context every backward's parameter gradients go to scratch buffers (see grad_buf)."""
+
+    def __enter__(self):
+        global _GRAD_SINK
+        self.prev, _GRAD_SINK = _GRAD_SINK, ({} if _GRAD_SINK is None else _GRAD_SINK)
+
+    def __exit__(self, *exc):
+        global _GRAD_SINK
+        _GRAD_SINK = self.prev
+
+
+class GradSinkFn(torch.autograd.Function):
+    """Identity on the outputs of a forward whose backward must leave every parameter gradient alone (the posterior
+    handed out by Dreamer.posterior(with_grad=True): only the gradient with respect to the observation is wanted).
+    Its backward runs before any node of that forward: it routes grad_buf to scratch buffers and asks the autograd
+    engine to end the routing when the whole backward has finished."""
+
+    @staticmethod
+    def forward(ctx, *xs):
+        ctx.set_materialize_grads(False)
+        return tuple(x.view_as(x) for x in xs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        global _GRAD_SINK
+        if _GRAD_SINK is None:
+            _GRAD_SINK = {}
+            torch.autograd.Variable._execution_engine.queue_callback(close_grad_sink)
+        return gs
 
 
 def _flat(x):
@@ -300,15 +345,53 @@ def _pad_last(w, n):
     return out
 
 
+def _stage_input(x, w, pad_shift):
+    """-> (the conv's input, the weight it runs with). pad_shift given: x is the raw image (its real channel count);
+    the input x - pad_shift zero-padded to a multiple of four channels is formed here, so the stage's backward hands
+    autograd a gradient of the image's own shape and no padded gradient exists."""
+    if pad_shift is not None:
+        x = k.pad_channels(x.contiguous(), (x.shape[-1] + 3) // 4 * 4, float(pad_shift))
+    return x, (w if x.shape[-1] == w.shape[-1] else _pad_last(w, x.shape[-1]))
+
+
+def _pooled_dx(ctx, x, w):
+    """True when the stage's input gradient is wanted and comes from the pooled gradient (k.conv2d_dgrad_pool): a
+    channel-padded input on a shape both pooled-gradient kernels take."""
+    Nb, H, W, Cx = x.shape
+    Co, kh, kw, Ci = w.shape
+    return (ctx.needs_input_grad[0] and Cx != Ci and POOL_COMPACT and k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0
+            and k.conv2d_dgrad_pool_takes(H, W, Co, Ci, kh, kw))
+
+
+def _stage_dx(ctx, x, w, dconv, dpool, amax):
+    """The stage's input gradient in the shape autograd expects: the raw image's channels (pad_shift route) or x's.
+    dconv None: from the pooled gradient; else conv2d_dgrad, on the zero-padded weight when x carries pad channels
+    (their gradient is zero: they meet zero weights only)."""
+    Cx, Ci = x.shape[-1], w.shape[-1]
+    if dconv is None:
+        dx = k.conv2d_dgrad_pool(dpool, amax, w)
+        if dx is None:
+            raise k.nat.NativeError("sd_conv2d_dgrad_pool refused a shape its query accepted")
+    else:
+        dx = k.conv2d_dgrad(dconv, w if Cx == Ci else _pad_last(w, Cx))
+    want = ctx.raw_c if ctx.raw_c is not None else Cx
+    if dx.shape[-1] > want:
+        dx = dx[..., :want].contiguous()
+    elif dx.shape[-1] < want:
+        dx = _pad_last(dx, want)
+    return dx
+
+
 class ConvPoolNormFn(torch.autograd.Function):
     """One ConvEncoder stage: Conv2dSamePad -> MaxPool2d(2) -> RMSNorm2D -> SiLU (networks.py:201-216), NHWC.
     Forward on the exact f32 MFMA kernels (the posterior samples depend on it); both backward contractions on the
     split-bf16 kernels (k.conv2d_wgrad / k.conv2d_dgrad, ~1e-5 relative)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, nw, nchw_flat):
+    def forward(ctx, x, w, b, nw, nchw_flat, pad_shift=None):
         # x may carry zero-padded channels (first layer: 3 -> 4); the weight is padded to match
-        wk = w if x.shape[-1] == w.shape[-1] else _pad_last(w, x.shape[-1])
+        ctx.raw_c = x.shape[-1] if pad_shift is not None else None
+        x, wk = _stage_input(x, w, pad_shift)
         fused = k.conv2d_fwd_pool(x.contiguous(), wk, b, nw, nchw_flat=nchw_flat) if FUSED_POOL else None
         if fused is None:
             conv = k.conv2d_fwd(x.contiguous(), wk, b)
@@ -327,15 +410,17 @@ class ConvPoolNormFn(torch.autograd.Function):
         Nb, H, W, _ = x.shape
         Co, kh, kw, Ci = w.shape
         acc = (grad_buf(w), grad_buf(b), Ci)  # the bwd-weight launches add into the gradients themselves
-        if not ctx.needs_input_grad[0] and POOL_COMPACT and k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0:
-            # first stage (no input gradient): the bwd-weight kernel expands the pooled gradient + argmax itself, so
-            # the full-resolution conv gradient (3/4 zeros) is never written or read
+        dpool = None
+        if _pooled_dx(ctx, x, w) or (not ctx.needs_input_grad[0] and POOL_COMPACT and
+                                     k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0):
+            # first stage: the bwd-weight kernel (and the input-gradient kernel, when the image's gradient is wanted)
+            # expands the pooled gradient + argmax itself, so the full-resolution conv gradient (3/4 zeros) is never
+            # written or read
             dpool = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw), nchw_flat=ctx.nchw_flat)
             k.conv2d_wgrad_pool(x, dpool, amax, kh, kw, acc=acc)
             dconv = None
         else:
             dconv = k.pool_rms_bwd(pooled, amax, nw, rstd, dy.contiguous(), H, W, grad_buf(nw), nchw_flat=ctx.nchw_flat)
-        Cx = x.shape[-1]
 
         def wgrad():
             k.conv2d_wgrad(x, dconv, kh, kw, acc=acc)
@@ -346,12 +431,8 @@ class ConvPoolNormFn(torch.autograd.Function):
             _DEFER.append((wgrad, (x, dconv)))
         else:
             wgrad()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if Cx != Ci:
-                raise NotImplementedError("input gradient through a channel-padded conv")
-            dx = k.conv2d_dgrad(dconv, w)
-        return dx, None, None, None, None
+        dx = _stage_dx(ctx, x, w, dconv, dpool, amax) if ctx.needs_input_grad[0] else None
+        return dx, None, None, None, None, None
 
 
 class FilmConvPoolNormFn(torch.autograd.Function):
@@ -362,8 +443,9 @@ class FilmConvPoolNormFn(torch.autograd.Function):
     beta = 0 every output and gradient equals ConvPoolNormFn's bit for bit."""
 
     @staticmethod
-    def forward(ctx, x, w, b, nw, gamma, beta, nchw_flat):
-        wk = w if x.shape[-1] == w.shape[-1] else _pad_last(w, x.shape[-1])
+    def forward(ctx, x, w, b, nw, gamma, beta, nchw_flat, pad_shift=None):
+        ctx.raw_c = x.shape[-1] if pad_shift is not None else None
+        x, wk = _stage_input(x, w, pad_shift)
         film = (gamma.contiguous(), beta.contiguous())
         fused = k.conv2d_fwd_pool(x.contiguous(), wk, b, nw, nchw_flat=nchw_flat, film=film) if FUSED_POOL else None
         if fused is None:
@@ -384,7 +466,9 @@ class FilmConvPoolNormFn(torch.autograd.Function):
         Co, kh, kw, Ci = w.shape
         acc = (grad_buf(w), grad_buf(b), Ci)
         film = (gamma, beta)
-        if not ctx.needs_input_grad[0] and POOL_COMPACT and k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0:
+        dpool = None
+        if _pooled_dx(ctx, x, w) or (not ctx.needs_input_grad[0] and POOL_COMPACT and
+                                     k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0):
             dpool, dgamma, dbeta = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw),
                                                           nchw_flat=ctx.nchw_flat, film=film)
             k.conv2d_wgrad_pool(x, dpool, amax, kh, kw, acc=acc)
@@ -402,12 +486,8 @@ class FilmConvPoolNormFn(torch.autograd.Function):
             _DEFER.append((wgrad, (x, dconv)))
         else:
             wgrad()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if x.shape[-1] != Ci:
-                raise NotImplementedError("input gradient through a channel-padded conv")
-            dx = k.conv2d_dgrad(dconv, w)
-        return dx, None, None, None, dgamma, dbeta, None
+        dx = _stage_dx(ctx, x, w, dconv, dpool, amax) if ctx.needs_input_grad[0] else None
+        return dx, None, None, None, dgamma, dbeta, None, None
 
 
 class RowBiasSiluFn(torch.autograd.Function):
