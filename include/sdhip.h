@@ -596,9 +596,10 @@ int sd_rssm_scan_step_kernel(const sd_rssm_scan* d, int which, int t, sd_stream 
  * RSSM.img_step (rssm.py:180-187: Deter.forward + prior logits + one-hot sample) — 9 launches per step. Every launch
  * is a row-tiled MFMA contraction whose A loader applies the previous layer's RMSNorm+SiLU on the fly (row rstd from
  * per-tile partial sums written by the producer's epilogue) and whose epilogue fuses bias, the GRU gate, the
- * samplers and the action branch (action_norm -> _dyn_in2 -> RMSNorm -> SiLU). Requirements: N % 64 == 0,
- * U == 256, D/G in {256, 512}, S*Kd % 64 == 0, Kd in {16, 32}, 2A <= 32 (A <= 16 discrete), 1..4 actor layers,
- * 1..4 img layers. feats (H1, N, S*Kd + D): row block t = 0 holds the start state on entry. */
+ * samplers and the action branch (action_norm -> _dyn_in2 -> RMSNorm -> SiLU). Requirements (else SD_ESHAPE, from
+ * sd_imagine_work_floats already and before any launch): N >= 1, U == 256, D <= 4096, D/G % 64 == 0 (the 64-column
+ * tiles of dyn_hid stay inside one block), S*Kd % 64 == 0, Kd in {16, 32}, 2A <= 32 (A <= 16 discrete), 1..4 actor
+ * layers, 1..4 img layers. feats (H1, N, S*Kd + D): row block t = 0 holds the start state on entry. */
 typedef struct sd_imagine {
   int N, H1, D, U, SK, Kd, G, A, act_discrete, actor_layers, img_layers;
   float eps, unimix, act_unimix, min_std, max_std;

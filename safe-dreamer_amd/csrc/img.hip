@@ -1342,14 +1342,27 @@ IWork iwork(const sd_imagine& d, float* base) {
   return w;
 }
 
-int icheck(const sd_imagine* d) {
-  if (!d || !d->feats || !d->actions || !d->work) return SD_EARG;
-  if (d->N < 1 || d->H1 < 1 || d->U != 256 || d->G < 1 || d->D % d->G || d->D > 4096) return SD_ESHAPE;
+// The shapes every launch of sd_imagine_run is tiled for (DESIGN.md § 2.1 lists which kernel needs which):
+//   Dg = D / G a multiple of 64: k_hid / k_hid_areg take 64-column tiles of hp and read the block of a tile as
+//     n0 / Dg, so a tile may not straddle two blocks of the block-diagonal weight (and Dg / 64 tiles per block > 0);
+//     it covers k_gate's 32-column tiles, the 32-deep k tiles of Dg and D, and the D / 64 row partials of hp;
+//   SK a multiple of 64 (k_prior_rw's 64-column workgroups, whole teams of Kd = 16 / 32 lanes; 32-deep k tiles of the
+//     dense _dyn_in1 / actor layer 0 contraction when S > 64);
+//   U = 256 (one wave per row at 4 columns a lane, 16 row partials of 16 columns);
+//   at most 32 actor output logits (k_action_rows<32>) and 16 actions (its _dyn_in2 stage).
+int ishape(const sd_imagine* d) {
+  if (d->N < 1 || d->H1 < 1 || d->U != 256 || d->G < 1 || d->D < 1 || d->D % d->G || d->D > 4096) return SD_ESHAPE;
   const int Dg = d->D / d->G;
-  if (Dg % 32 || Dg < 32 || d->SK % 64 || (d->Kd != 16 && d->Kd != 32) || d->SK % d->Kd) return SD_ESHAPE;
+  if (Dg % 64 || d->SK < 64 || d->SK % 64 || (d->Kd != 16 && d->Kd != 32)) return SD_ESHAPE;
   if (d->A < 1 || (d->act_discrete ? d->A > 16 : 2 * d->A > 32)) return SD_ESHAPE;
   if (d->actor_layers < 1 || d->actor_layers > 4 || d->img_layers < 1 || d->img_layers > 4) return SD_ESHAPE;
-  if ((d->SK + d->D) % 32) return SD_ESHAPE;
+  return SD_OK;
+}
+
+int icheck(const sd_imagine* d) {
+  if (!d || !d->feats || !d->actions || !d->work) return SD_EARG;
+  const int rc = ishape(d);
+  if (rc) return rc;
   if (d->t_begin < 0 || d->t_begin >= (d->t_end > 0 ? d->t_end : d->H1) || d->t_end > d->H1) return SD_EARG;
   return SD_OK;
 }
@@ -1374,6 +1387,8 @@ extern "C" int sd_imagine_noise(const sd_imagine* dp, float* noise, float* noise
 
 extern "C" int sd_imagine_work_floats(const sd_imagine* d) {
   if (!d) return SD_EARG;
+  const int rc = ishape(d);  // the shape gate, before any pointer exists: an unsupported shape gets no workspace
+  if (rc) return rc;
   return (int)iwork(*d, nullptr).total;
 }
 

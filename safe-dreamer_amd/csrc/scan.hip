@@ -679,6 +679,19 @@ template <int KD>
 SD_DEV float sampler_bwd(float l, float gn, float ds, float unimix, int lt) {
   return sampler_bwd_tail<KD>(sampler_fwd<KD>(l, gn, unimix, lt), ds, unimix);
 }
+// The same two halves out of line, for a kernel that holds more than one sampler element per thread (k_carry<64>: two).
+// Inlined once per element, hipcc compiled the copies differently — unimix_forward's pp = p (1 - u) + u / K came out
+// as v_fmac_f32 in one and as v_pk_mul_f32 + v_add_f32 in the other — so rows 8..15 of a 16-row tile differed in
+// the last bit from the same rows computed as rows 0..7 of a smaller tile. Through one function body every element
+// runs the same instructions, whatever the compiler picks for them.
+template <int KD>
+__device__ __noinline__ STFwd sampler_fwd_shared(float l, float gn, float unimix, int lt) {
+  return sampler_fwd<KD>(l, gn, unimix, lt);
+}
+template <int KD>
+__device__ __noinline__ float sampler_bwd_tail_shared(STFwd f, float ds, float unimix) {
+  return sampler_bwd_tail<KD>(f, ds, unimix);
+}
 
 // incoming gradient of posterior element (t, row, col) of a width-W output: time-major, or batch-major (bm_grads) plus
 // an optional second summand g2 (rows of ld_g2 floats), summed as g + g2 (the caller's former torch.add order)
@@ -1061,7 +1074,10 @@ __global__ __launch_bounds__(NTHR) void k_carry(sd_rssm_scan d, Work w, int t) {
   if (!p0) {
 #pragma unroll
     for (int k = 0; k < NE; ++k)
-      if (tid + NTHR * k < MR * KD) sf[k] = sampler_fwd<KD>(e0[k], gn[k], d.unimix, (tid + NTHR * k) % KD);
+      if (tid + NTHR * k < MR * KD) {
+        if constexpr (NE > 1) sf[k] = sampler_fwd_shared<KD>(e0[k], gn[k], d.unimix, (tid + NTHR * k) % KD);
+        else sf[k] = sampler_fwd<KD>(e0[k], gn[k], d.unimix, (tid + NTHR * k) % KD);
+      }
   }
   // d_xcat part = sum of the slabs (k_dx01's order)
   f32x4 dx[NU];
@@ -1104,7 +1120,10 @@ __global__ __launch_bounds__(NTHR) void k_carry(sd_rssm_scan d, Work w, int t) {
         if (ev) w.ch[(long)ger * D + n0 + lt] = rs[k] ? 0.f : e0[k] + C[er * KD + lt];
       } else {
         const float cs = rs[k] ? 0.f : C[er * KD + lt];
-        const float dlv = sampler_bwd_tail<KD>(sf[k], ev ? e1[k].value(d, d.d_stoch, d.d_stoch2) + cs : 0.f, d.unimix);
+        const float ds = ev ? e1[k].value(d, d.d_stoch, d.d_stoch2) + cs : 0.f;
+        float dlv;
+        if constexpr (NE > 1) dlv = sampler_bwd_tail_shared<KD>(sf[k], ds, d.unimix);
+        else dlv = sampler_bwd_tail<KD>(sf[k], ds, d.unimix);
         if (ev) d.dl[(long)tp * B * SK + (long)ger * SK + n0 + lt] = e2[k].value(d, d.d_logit, nullptr) + dlv;
       }
     }

@@ -9,6 +9,11 @@ from __future__ import annotations
 import ctypes
 import os
 
+# torch first: libsdhip.so must bind to the HIP runtime torch loads (a torch wheel brings its own copy). Loaded before
+# torch, the library pulls in the system's copy, torch then loads a second one, and the library's launches answer
+# hipErrorNoDevice (100) — which is what __graft_entry__.build() followed by smoke() in one process ran into.
+import torch  # noqa: F401
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDHIP_LIB", os.path.join(_HERE, "_lib", "libsdhip.so"))
 

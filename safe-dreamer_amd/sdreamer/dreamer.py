@@ -1343,7 +1343,8 @@ class Dreamer(nn.Module):
         if a.dist_name not in ("bounded_normal", "onehot") or r._deter % r._blocks or r._deter > 4096:
             return False
         A = self.act_dim
-        return (r._deter // r._blocks) % 32 == 0 and r.flat_stoch % 64 == 0 and r._discrete in (16, 32) and \
+        # csrc/img.hip ishape(): k_hid's 64-column tiles may not straddle two blocks of the block-diagonal weight
+        return (r._deter // r._blocks) % 64 == 0 and r.flat_stoch % 64 == 0 and r._discrete in (16, 32) and \
             (A <= 16 if self.act_discrete else 2 * A <= 32) and 1 <= a.mlp.n <= 4 and 1 <= r._img_layers <= 4 and \
             a.last.weight.shape[0] <= 32
 
