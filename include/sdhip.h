@@ -233,13 +233,15 @@ typedef struct sd_wgrad_acc {
   float* db;
   int ci_w;
 } sd_wgrad_acc;
-/* dw_db (Co, kh*kw*Ci + 1) = [dW | d bias]; ksplit > 1 needs workspace >= ksplit*Co*(kh*kw*Ci+1) floats */
+/* dw_db (Co, kh*kw*Ci + 1) = [dW | d bias]; workspace >= slabs*Co*(kh*kw*Ci+1) floats, slabs from
+ * sd_conv2d_wgrad_slabs (SD_EARG below that) */
 int sd_conv2d_wgrad(const float* in, const float* dout, float* dw_db, float* workspace, long ws_floats, int ksplit,
                     int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad, int ups, const sd_wgrad_acc* acc,
                     sd_stream stream);
-/* partial-slab count sd_conv2d_wgrad uses for this request (workspace >= slabs * Co * (kh*kw*Ci + 1) floats when
- * slabs > 1): stride-1 convs with Co % 16 == 0 take a direct kernel (dy rows + input patch staged in LDS, no im2col
- * re-reads) whose split is fixed by the library; others use `ksplit` over the im2col implicit GEMM. */
+/* partial-slab count sd_conv2d_wgrad uses for this request (workspace >= slabs * Co * (kh*kw*Ci + 1) floats, one
+ * slab included: the direct kernel always writes its slabs and reduces them; only the implicit GEMM with one slab leaves
+ * the workspace unread): stride-1 convs with Co % 16 == 0 take a direct kernel (dy rows + input patch staged in LDS, no
+ * im2col re-reads) whose split is fixed by the library; others use `ksplit` over the im2col implicit GEMM. */
 int sd_conv2d_wgrad_slabs(int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int ups, int ksplit);
 /* bwd-weight of a pooled ConvEncoder stage from (dpool, argmax) of sd_pool_rms_bwd_compact (the conv gradient is
  * expanded inside the direct kernel while staging). _slabs: workspace slabs (each Co x (kh*kw*Ci+1) floats), 0 when

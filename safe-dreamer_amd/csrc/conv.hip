@@ -1602,6 +1602,18 @@ __global__ void pool_rms_bwd(const float* __restrict__ pooled, const uint8_t* __
             const int yy = 2 * yo + (q >> 1), xx = 2 * xo + (q & 1);
             dx[(((long)n * H + yy) * W + xx) * C + c] = q == bi ? dp : 0.f;
           }
+          // an odd H or W: MaxPool2d(2) floors, so the last row / column belongs to no window and its gradient is
+          // zero. The windows at the edge write it (dx is not cleared beforehand); even sizes take neither branch.
+          const bool ex = (W & 1) && xo == Wo - 1, ey = (H & 1) && yo == Ho - 1;
+          if (ex) {
+            dx[(((long)n * H + 2 * yo) * W + W - 1) * C + c] = 0.f;
+            dx[(((long)n * H + 2 * yo + 1) * W + W - 1) * C + c] = 0.f;
+          }
+          if (ey) {
+            dx[(((long)n * H + H - 1) * W + 2 * xo) * C + c] = 0.f;
+            dx[(((long)n * H + H - 1) * W + 2 * xo + 1) * C + c] = 0.f;
+            if (ex) dx[(((long)n * H + H - 1) * W + W - 1) * C + c] = 0.f;
+          }
         }
       }
     }
@@ -1771,6 +1783,9 @@ bool direct_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, int ups, 
   pl.ws = JB <= 7;  // few column blocks: split the pixels over the waves instead
   pl.nbw = pl.ws ? 7 : JB <= 16 ? 2 : JB <= 32 ? 4 : JB <= 56 ? 7 : (Co <= 48 ? 10 : 7);
   pl.gx = pl.ws ? 1 : (JB + NW_D * pl.nbw - 1) / (NW_D * pl.nbw);
+  // the wave-split kernel sums its NW_D waves' 16 x 16 tiles through the first NW_D * 4 * 64 floats of LDS at the end:
+  // a block that stages less (a 4 x 4 image of 4 channels: 2176 bytes) still gets that much
+  if (pl.ws && pl.lds < (size_t)NW_D * 4 * 64 * sizeof(float)) pl.lds = (size_t)NW_D * 4 * 64 * sizeof(float);
   const int blocks = Nb * (H / pl.R);
   pl.gy = 256 / pl.gx;
   if (pl.gy > blocks) pl.gy = blocks;
@@ -2035,6 +2050,14 @@ extern "C" int sd_pool_rms_fwd(const float* x, const float* w, float* pooled, ui
   return SD_OK;
 }
 
+// An image of one row or one column has no 2x2 window: the conv gradient is all zeros and no pooled pixel exists to
+// write it (the degenerate case only; every other shape is written by the kernel itself, odd edges included).
+static int pool_rms_bwd_empty(float* dx, int Nb, int H, int W, int C, hipStream_t s) {
+  const long n = (long)Nb * H * W * C;
+  if (n <= 0 || ((H / 2) > 0 && (W / 2) > 0)) return SD_OK;
+  return hipMemsetAsync(dx, 0, (size_t)n * sizeof(float), s) == hipSuccess ? SD_OK : SD_EARG;
+}
+
 extern "C" int sd_pool_rms_bwd_blocks(int Nb, int H, int W) {
   const long P = (long)Nb * (H / 2) * (W / 2);
   long b = (P + 15) / 16;
@@ -2047,6 +2070,7 @@ extern "C" int sd_pool_rms_bwd(const float* pooled, const uint8_t* amax, const f
   hipStream_t s = (hipStream_t)stream_;
   if (C > 128) return SD_ESHAPE;
   const int grid = sd_pool_rms_bwd_blocks(Nb, H, W);
+  if (pool_rms_bwd_empty(dx, Nb, H, W, C, s) != SD_OK) return SD_EARG;
   SD_POOL_SWITCH(pool_rms_bwd, grid, pooled, amax, w, rstd, dy, dx, dw_partial, Nb, H, W, C, nchw_flat)
   SD_LAUNCH_CHECK();
   // two-pass column sum of the per-block dw partials; its chunk workspace follows them in dw_partial
@@ -2113,6 +2137,7 @@ static int pool_rms_bwd_film_impl(const float* pooled, const uint8_t* amax, cons
   const int grid = sd_pool_rms_bwd_blocks(Nb, H, W);
   const FilmNW f{w, gamma, beta, ipc};
   const int rows = Nb / ipc, nblk = film_grad_blocks(ipc, H, W);
+  if (!COMPACT && pool_rms_bwd_empty(dx, Nb, H, W, C, s) != SD_OK) return SD_EARG;
   const dim3 fgrid(nblk, rows);
 #define SD_FILM_BWD(V)                                                                                               \
   pool_rms_bwd<16, V, COMPACT, FilmNW><<<grid, 256, 0, s>>>(pooled, amax, f, rstd, dy, dx, dw_partial, Nb, H, W, C,  \

@@ -615,9 +615,10 @@ def conv2d_wgrad(x, dout, kh, kw, ups=0, pad=None, fast=True, acc=None):
         ks = nat.fns["sd_conv2d_wgrad_bf16x3_slabs"](Nb, H, W, Ci, Co, kh, kw, ups)
         if ks > 0:
             out = torch.empty(Co, J + 1, dtype=torch.float32, device=x.device)
-            ws = torch.empty(ks * Co * (J + 1), dtype=torch.float32, device=x.device) if ks > 1 else None
-            if nat.call_shaped("sd_conv2d_wgrad_bf16x3", p(_c(x)), p(_c(dout)), p(out), p(ws),
-                               ws.numel() if ws is not None else 0, Nb, H, W, Ci, Co, kh, kw, pad, ap, stream()):
+            # the direct kernels write a slab per row-block group and reduce them: one slab needs its workspace too
+            ws = torch.empty(ks * Co * (J + 1), dtype=torch.float32, device=x.device)
+            if nat.call_shaped("sd_conv2d_wgrad_bf16x3", p(_c(x)), p(_c(dout)), p(out), p(ws), ws.numel(),
+                               Nb, H, W, Ci, Co, kh, kw, pad, ap, stream()):
                 return None if acc is not None else out
     pixels = dout.numel() // Co
     ks = max(1, min(256, pixels // 4096))
@@ -625,8 +626,10 @@ def conv2d_wgrad(x, dout, kh, kw, ups=0, pad=None, fast=True, acc=None):
     ks = max(1, min(ks, max(1, 1024 // tiles)))
     out = torch.empty(Co, J + 1, dtype=torch.float32, device=x.device)
     ks = nat.fns["sd_conv2d_wgrad_slabs"](Nb, H, W, Ci, Co, kh, kw, ups, ks)
-    ws = torch.empty(ks * Co * (J + 1), dtype=torch.float32, device=x.device) if ks > 1 else None
-    nat.call("sd_conv2d_wgrad", p(_c(x)), p(_c(dout)), p(out), p(ws), ws.numel() if ws is not None else 0, ks,
+    # (ks == 1 is one slab of the f32 direct kernel, which needs it, or the implicit GEMM unsplit, which does not: the
+    # query does not tell them apart)
+    ws = torch.empty(ks * Co * (J + 1), dtype=torch.float32, device=x.device)
+    nat.call("sd_conv2d_wgrad", p(_c(x)), p(_c(dout)), p(out), p(ws), ws.numel(), ks,
              Nb, H, W, Ci, Co, kh, kw, pad, ups, ap, stream())
     del keep
     return None if acc is not None else out
