@@ -1060,7 +1060,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad3(GemmArgs g, Geom G, int lw
   KCSplit<DenseKCB<BN>, BN> lb(lb0);
   f32x4 acc[2][BN / 16];
   sdb::gemm3_mainloop<BM, BN, 32, BN>(la, lb, 0, g.K, acc);
-  sdb::gemm3_epilogue<BM, BN, 32, BN>(g, acc, bm0, 0, 0, 0);
+  epilogue16<BM, BN, 32, BN>(g, acc, bm0, 0, 0, 0);
 }
 
 // bwd-data as a DIRECT convolution on split-bf16 MFMAs: conv_dgrad3's contraction (dIn = conv_same(dOut, flipped W),
@@ -1725,23 +1725,19 @@ __global__ void sumpool2(const float* __restrict__ du, float* __restrict__ din, 
   din[t] = (b[0] + b[C]) + (b[(long)W2 * C] + b[(long)W2 * C + C]);
 }
 
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 template <int BM, int BN, int WM, int WN>
 void fwd_tile(GemmArgs& g, Geom& G, bool va, bool vb, hipStream_t s) {
   dim3 grid(sd_cdiv(g.N, BN), sd_cdiv(g.M, BM), 1);
-  if (va && vb) conv_fwd_kernel<BM, BN, WM, WN, true, true><<<grid, 256, 0, s>>>(g, G);
-  else if (vb) conv_fwd_kernel<BM, BN, WM, WN, false, true><<<grid, 256, 0, s>>>(g, G);
-  else conv_fwd_kernel<BM, BN, WM, WN, false, false><<<grid, 256, 0, s>>>(g, G);
+  // (the callers' va implies vb)
+  with_bools([&](auto VA, auto VB) { conv_fwd_kernel<BM, BN, WM, WN, VA() && VB(), VB()><<<grid, 256, 0, s>>>(g, G); },
+             va, vb);
 }
 
 template <int BM, int BN, int WM, int WN>
 void wgrad_tile(GemmArgs& g, Geom& G, int J, bool va, bool vb, hipStream_t s) {
   dim3 grid(sd_cdiv(g.N, BN), sd_cdiv(g.M, BM), g.ksplit);
-  if (va && vb) conv_wgrad_kernel<BM, BN, WM, WN, true, true><<<grid, 256, 0, s>>>(g, G, J);
-  else if (va) conv_wgrad_kernel<BM, BN, WM, WN, true, false><<<grid, 256, 0, s>>>(g, G, J);
-  else if (vb) conv_wgrad_kernel<BM, BN, WM, WN, false, true><<<grid, 256, 0, s>>>(g, G, J);
-  else conv_wgrad_kernel<BM, BN, WM, WN, false, false><<<grid, 256, 0, s>>>(g, G, J);
+  with_bools([&](auto VA, auto VB) { conv_wgrad_kernel<BM, BN, WM, WN, VA(), VB()><<<grid, 256, 0, s>>>(g, G, J); },
+             va, vb);
 }
 
 int vpt_for(int C, int T) { int v = (C + T - 1) / T; return v <= 1 ? 1 : v <= 2 ? 2 : v <= 4 ? 4 : 8; }
@@ -1849,8 +1845,8 @@ extern "C" int sd_conv2d_fwd(const float* in, const float* w, const float* bias,
   g.B = w; g.C = out; g.bias = bias; g.ldb = (long)kh * kw * Ci; g.ldc = Co;
   g.M = Nb * G.Hg * G.Wg; g.N = Co; g.K = kh * kw * Ci; g.batch = 1; g.ksplit = 1; g.kchunk = g.K;
   g.alpha = 1.f; g.beta = 0.f;
-  const bool vb = (((long)kh * kw * Ci) % 4 == 0) && al16(w);
-  const bool va = (Ci % 4 == 0) && al16(in) && vb;
+  const bool vb = (((long)kh * kw * Ci) % 4 == 0) && aligned16(w);
+  const bool va = (Ci % 4 == 0) && aligned16(in) && vb;
   const int lw = ilog2_exact(G.Wg), lhw = ilog2_exact(G.Hg * G.Wg);
   if (va && lw >= 0 && lhw >= 0 && g.K / 4 <= MAX_TAPQ && (Co == 32 || Co == 48 || Co == 64 || Co == 16)) {
     const dim3 grid(sd_cdiv(g.M, 128));
@@ -1885,19 +1881,19 @@ static int fwd_pool_impl(const float* in, const float* w, const float* bias, NW 
   g.B = w; g.bias = bias; g.ldb = (long)kh * kw * Ci; g.ldc = Co;
   g.M = Nb * Hs * Ws; g.N = Co; g.K = kh * kw * Ci; g.batch = 1; g.ksplit = 1; g.kchunk = g.K;
   g.alpha = 1.f; g.beta = 0.f;
-  const bool vb = (((long)kh * kw * Ci) % 4 == 0) && al16(w);
-  const bool va = (Ci % 4 == 0) && al16(in) && vb;
+  const bool vb = (((long)kh * kw * Ci) % 4 == 0) && aligned16(w);
+  const bool va = (Ci % 4 == 0) && aligned16(in) && vb;
   const int lw = ilog2_exact(Ws), lhw = ilog2_exact(Hs * Ws);
   if (!va || lw < 1 || lhw < 0 || g.K / 4 > MAX_TAPQ || Hs % 2 || 128 % (2 * Ws) || g.M % 128) return SD_ESHAPE;
   const dim3 grid(g.M / 128);
   const bool es = (long)Nb * Hs * Ws * Ci < (1L << 29);  // buffer offsets < 2 GiB
-  if (es && Co == 48 && Ci == 32 && Ws == 32 && kh == 5 && kw == 5 && pad == 2 && Hs % 4 == 0 && al16(in)) {
+  if (es && Co == 48 && Ci == 32 && Ws == 32 && kh == 5 && kw == 5 && pad == 2 && Hs % 4 == 0 && aligned16(in)) {
     conv_fwd_direct_pool<48, 32, 5, 5, NW><<<g.M / 128, 256, 0, s>>>(g, G, lhw, nw, pooled, amax, y, rstd, eps,
                                                                      nchw_flat);
     SD_LAUNCH_CHECK();
     return SD_OK;
   }
-  if (es && Co == 32 && Ci == 4 && Ws == 64 && kh == 5 && kw == 5 && pad == 2 && Hs % 2 == 0 && al16(in)) {
+  if (es && Co == 32 && Ci == 4 && Ws == 64 && kh == 5 && kw == 5 && pad == 2 && Hs % 2 == 0 && aligned16(in)) {
     // one round of resident workgroups (4 per CU): tpw tiles each. (The round-5 grid was 16 tiles per workgroup: 2048
     // workgroups at 1024 images, 2.67 rounds of the 768 then resident.)
     const int tiles = g.M / 128, tpw = sd_cdiv(tiles, 1024), nwg = sd_cdiv(tiles, tpw);
@@ -1956,8 +1952,8 @@ extern "C" int sd_conv2d_wgrad(const float* in, const float* dout, float* dw_db,
   long kc = ((long)g.K + ks - 1) / ks;
   g.kchunk = (int)((kc + BK - 1) / BK * BK);
   g.alpha = 1.f; g.beta = 0.f;
-  const bool va = al16(dout) && Co % 4 == 0;
-  const bool vb = (Ci % 4 == 0) && al16(in);
+  const bool va = aligned16(dout) && Co % 4 == 0;
+  const bool vb = (Ci % 4 == 0) && aligned16(in);
   DirectPlan pl;
   if (va && vb && direct_plan(Nb, Hs, Ws, Ci, Co, kh, kw, ups, pl))
     return wgrad_direct(in, dout, dw_db, workspace, ws_floats, Nb, Hs, Ws, Ci, Co, kh, kw, pad, J, ilog2_exact(G.Wg),
@@ -1966,9 +1962,7 @@ extern "C" int sd_conv2d_wgrad(const float* in, const float* dout, float* dw_db,
   else wgrad_tile<64, 64, 32, 32>(g, G, J, va, vb, s);
   SD_LAUNCH_CHECK();
   if (ks > 1) {
-    long total = (long)g.M * g.N;
-    int blocks = (int)((total + 255) / 256);
-    gemm_reduce_kernel<<<blocks, 256, 0, s>>>(g);
+    launch_reduce(g, s, false);
     SD_LAUNCH_CHECK();
   }
   if (acc.dw) {  // the implicit-GEMM path wrote dw_db: one pass adds it into the gradients
@@ -2010,7 +2004,8 @@ extern "C" int sd_conv2d_wgrad_pool(const float* in, const float* dpool, const u
   if (!pool_plan(Nb, H, W, Ci, Co, kh, kw, pl))
     return SD_ESHAPE;
   // amax is read as uint32 words (4 pooled pixels' argmax bytes per load)
-  if (!al16(dpool) || !al16(in) || Co % 4 || Ci % 4 || !amax || reinterpret_cast<uintptr_t>(amax) % 4) return SD_EARG;
+  if (!aligned16(dpool) || !aligned16(in) || Co % 4 || Ci % 4 || !amax || reinterpret_cast<uintptr_t>(amax) % 4)
+    return SD_EARG;
   return wgrad_direct(in, dpool, dw_db, workspace, ws_floats, Nb, H, W, Ci, Co, kh, kw, pad, kh * kw * Ci,
                       ilog2_exact(W), pl, (hipStream_t)stream_, amax, acc);
 }
@@ -2279,7 +2274,7 @@ extern "C" int sd_conv2d_dgrad_bf16x3(const float* dout, const float* wflip, flo
   g.M = Nb * Hs * Ws; g.N = Co; g.K = kh * kw * Ci; g.batch = 1; g.ksplit = 1; g.kchunk = g.K;
   g.alpha = 1.f; g.beta = 0.f;
   const int lw = ilog2_exact(Ws), lhw = ilog2_exact(Hs * Ws);
-  if (Ci % 4 || !al16(dout) || !al16(wflip) || lw < 0 || lhw < 0 || g.K / 4 > MAX_TAPQ ||
+  if (Ci % 4 || !aligned16(dout) || !aligned16(wflip) || lw < 0 || lhw < 0 || g.K / 4 > MAX_TAPQ ||
       (long)Nb * Hs * Ws * Ci >= (1L << 29))
     return SD_ESHAPE;
   const dim3 grid(sd_cdiv(g.M, 128));
@@ -2375,7 +2370,7 @@ static int fwd_pool6_impl(const float* in, const void* wsplit3, const float* bia
                           float eps, int nchw_flat, sd_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (Nb <= 0) return SD_OK;
-  if (kh != 5 || kw != 5 || pad != 2 || Hs != Ws || Hs % 2 || !al16(in) || !al16(wsplit3)) return SD_ESHAPE;
+  if (kh != 5 || kw != 5 || pad != 2 || Hs != Ws || Hs % 2 || !aligned16(in) || !aligned16(wsplit3)) return SD_ESHAPE;
   Geom G{in, Nb, Hs, Ws, Ci, Hs, Ws, kh, kw, pad, 0};
   GemmArgs g{};
   g.bias = bias; g.M = Nb * Hs * Ws; g.N = Co; g.K = kh * kw * Ci;
@@ -2442,7 +2437,8 @@ extern "C" int sd_conv2d_dgrad_direct(const float* dout, const void* wsplit, flo
                                       int Ci, int Co, int kh, int kw, int pad, sd_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (Nb <= 0) return SD_OK;
-  if (kh != 5 || kw != 5 || pad != 2 || Hs != Ws || !al16(dout) || !al16(wsplit) || !al16(din)) return SD_ESHAPE;
+  if (kh != 5 || kw != 5 || pad != 2 || Hs != Ws || !aligned16(dout) || !aligned16(wsplit) || !aligned16(din))
+    return SD_ESHAPE;
   const __bf16* wsp = static_cast<const __bf16*>(wsplit);
   // 32 x 32 images: 512-pixel tiles (16 rows) over 8 waves, one workgroup per CU
   if (Ci == 48 && Co == 32 && Ws == 32) return dgrad_direct_launch<48, 2, 5, 16, 512>(dout, wsp, din, Nb, Hs, pad, s);
@@ -2471,7 +2467,7 @@ extern "C" int sd_conv2d_wgrad_pool_bf16x3(const float* in, const float* dpool, 
   if (acc.dw && (!acc.db || acc.ci_w < 1 || acc.ci_w > Ci)) return SD_EARG;
   DirectPlan pl;
   if (!pool3_plan(Nb, H, W, Ci, Co, kh, kw, pl)) return SD_ESHAPE;
-  if (!al16(dpool) || !al16(in) || !amax || reinterpret_cast<uintptr_t>(amax) % 4) return SD_EARG;
+  if (!aligned16(dpool) || !aligned16(in) || !amax || reinterpret_cast<uintptr_t>(amax) % 4) return SD_EARG;
   return wgrad3_direct(in, dpool, dw_db, workspace, ws_floats, Nb, H, W, Ci, Co, kh, kw, pad, pl,
                        (hipStream_t)stream_, acc, amax);
 }
@@ -2484,7 +2480,7 @@ extern "C" int sd_conv2d_wgrad_bf16x3(const float* in, const float* dout, float*
   const sd_wgrad_acc acc = acc_p ? *acc_p : sd_wgrad_acc{nullptr, nullptr, 0};
   if (acc.dw && (!acc.db || acc.ci_w < 1 || acc.ci_w > Ci)) return SD_EARG;
   DirectPlan pl;
-  if (!direct3_plan(Nb, Hs, Ws, Ci, Co, kh, kw, 0, pl) || !al16(in) || !al16(dout)) return SD_ESHAPE;
+  if (!direct3_plan(Nb, Hs, Ws, Ci, Co, kh, kw, 0, pl) || !aligned16(in) || !aligned16(dout)) return SD_ESHAPE;
   return wgrad3_direct(in, dout, dw_db, workspace, ws_floats, Nb, Hs, Ws, Ci, Co, kh, kw, pad, pl, s, acc);
 }
 

@@ -8,12 +8,12 @@
 // cross-correlation (dreamer.py:528). Operand layout is a compile-time choice (A_K / B_K: "k is the contiguous
 // index"), so every global->LDS copy is a coalesced float4 stream.
 //
-// Tiling: 256 threads = 4 waves, a BM x BN block tile, BK = 16, register-staged double-buffered LDS.
-// LDS image per operand is [row][BK+4] (80-byte rows): each lane reads its 8 k-values for one MFMA row as two
-// ds_read_b128, conflict-free (5 is odd -> the 16 lanes of a b128 group hit 16 distinct 16-B slots).
-// The MFMA's k order is permuted (lane half h supplies k = s + 8h at step s) — the product is a sum, so any
+// Tiling: 256 threads = 4 waves, a BM x BN block tile, BK = 32, register-staged double-buffered LDS.
+// LDS image per operand is [row][BK+4] (144-byte rows): each lane reads its 16 k-values for one MFMA row as four
+// ds_read_b128, conflict-free (9 is odd -> the 16 lanes of a b128 group hit 16 distinct 16-B slots).
+// The MFMA's k order is permuted (lane half h supplies k = s + 16h at step s) — the product is a sum, so any
 // k order is valid as long as A and B agree.
-// Split-K writes fp32 partial slabs that sd_gemm_reduce sums in a fixed order (deterministic, no atomics).
+// Split-K writes fp32 partial slabs that gemm_reduce_kernel sums in a fixed order (deterministic, no atomics).
 #include "common.h"
 #include "sdhip.h"
 
@@ -25,10 +25,8 @@ using namespace sdg;
 template <int BM, int BN, int WM, int WN, bool AK, bool BKC>
 void launch_tile(const GemmArgs& g, bool va, bool vb, hipStream_t st) {
   dim3 grid(sd_cdiv(g.N, BN), sd_cdiv(g.M, BM), g.batch * g.ksplit);
-  if (va && vb) gemm_kernel<BM, BN, WM, WN, AK, BKC, true, true><<<grid, 256, 0, st>>>(g);
-  else if (va) gemm_kernel<BM, BN, WM, WN, AK, BKC, true, false><<<grid, 256, 0, st>>>(g);
-  else if (vb) gemm_kernel<BM, BN, WM, WN, AK, BKC, false, true><<<grid, 256, 0, st>>>(g);
-  else gemm_kernel<BM, BN, WM, WN, AK, BKC, false, false><<<grid, 256, 0, st>>>(g);
+  with_bools([&](auto VA, auto VB) { gemm_kernel<BM, BN, WM, WN, AK, BKC, VA(), VB()><<<grid, 256, 0, st>>>(g); },
+             va, vb);
 }
 
 template <bool AK, bool BKC>
@@ -40,8 +38,6 @@ void launch_layout(const GemmArgs& g, int tile, bool va, bool vb, hipStream_t st
     default: launch_tile<128, 64, 64, 32, AK, BKC>(g, va, vb, st); break;
   }
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---------------------------------------------------------------- skinny GEMM (M <= 32), e.g. the per-step
 // contractions of the RSSM observe scan (B = 16 rows). Weight-streaming bound: no LDS staging, each lane loads
@@ -71,22 +67,10 @@ __global__ __launch_bounds__(256) void gemm_skinny(GemmArgs g) {
       const int kk = k + 32 * i + 4 * h;
       f32x4 x = {0.f, 0.f, 0.f, 0.f}, y = {0.f, 0.f, 0.f, 0.f};
       if (kk < kend) {
-        if (mv) {
-          const float* q = A + (long)m * g.lda + kk;
-          if (VA && kk + 3 < kend) x = *reinterpret_cast<const f32x4*>(q);
-          else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) if (kk + j < kend) x[j] = q[j];
-          }
-        }
+        if (mv) x = load4_guard<VA>(A + (long)m * g.lda + kk, kk, kend);
         if (nv) {
           if (BKC) {
-            const float* q = Bp + (long)n * g.ldb + kk;
-            if (VB && kk + 3 < kend) y = *reinterpret_cast<const f32x4*>(q);
-            else {
-#pragma unroll
-              for (int j = 0; j < 4; ++j) if (kk + j < kend) y[j] = q[j];
-            }
+            y = load4_guard<VB>(Bp + (long)n * g.ldb + kk, kk, kend);
           } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) if (kk + j < kend) y[j] = Bp[(long)(kk + j) * g.ldb + n];
@@ -111,14 +95,10 @@ __global__ __launch_bounds__(256) void gemm_skinny(GemmArgs g) {
     const float v = (red[0][r][lane] + red[1][r][lane]) + (red[2][r][lane] + red[3][r][lane]);
     const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
     if (row < g.M && nv) {
-      if (g.ksplit > 1) {
-        g.ws[((long)split * g.batch + b) * (long)g.M * g.N + (long)row * g.N + n] = g.alpha * v;
-      } else {
-        float o = g.alpha * v + (g.bias ? g.bias[(long)b * g.sBias + n] : 0.f);
-        float* c = g.C + (long)b * g.sC + (long)row * g.ldc + n;
-        if (g.beta != 0.f) o += g.beta * *c;
-        *c = o;
-      }
+      const bool part = g.ksplit > 1;
+      store_c(part ? g.ws + ((long)split * g.batch + b) * (long)g.M * g.N + (long)row * g.N + n : nullptr,
+              g.C + (long)b * g.sC + (long)row * g.ldc + n, v, g.alpha,
+              (!part && g.bias) ? g.bias[(long)b * g.sBias + n] : 0.f, g.beta);
     }
   }
 }
@@ -150,22 +130,10 @@ __global__ __launch_bounds__(512) void gemm_m16(GemmArgs g) {
       const int kk = k + 16 * NW * i + 4 * q;
       f32x4 x = {0.f, 0.f, 0.f, 0.f}, y = {0.f, 0.f, 0.f, 0.f};
       if (kk < kend) {
-        if (mv) {
-          const float* p = A + (long)m * g.lda + kk;
-          if (VA && kk + 3 < kend) x = *reinterpret_cast<const f32x4*>(p);
-          else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) if (kk + j < kend) x[j] = p[j];
-          }
-        }
+        if (mv) x = load4_guard<VA>(A + (long)m * g.lda + kk, kk, kend);
         if (nv) {
           if (BKC) {
-            const float* p = Bp + (long)n * g.ldb + kk;
-            if (VB && kk + 3 < kend) y = *reinterpret_cast<const f32x4*>(p);
-            else {
-#pragma unroll
-              for (int j = 0; j < 4; ++j) if (kk + j < kend) y[j] = p[j];
-            }
+            y = load4_guard<VB>(Bp + (long)n * g.ldb + kk, kk, kend);
           } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) if (kk + j < kend) y[j] = Bp[(long)(kk + j) * g.ldb + n];
@@ -190,40 +158,25 @@ __global__ __launch_bounds__(512) void gemm_m16(GemmArgs g) {
     for (int w = 0; w < NW; ++w) v += red[w][r][lane];
     const int row = 4 * q + r;
     if (row < g.M && nv) {
-      if (g.ksplit > 1) {
-        g.ws[((long)split * g.batch + b) * (long)g.M * g.N + (long)row * g.N + n] = g.alpha * v;
-      } else {
-        float o = g.alpha * v + (g.bias ? g.bias[(long)b * g.sBias + n] : 0.f);
-        float* c = g.C + (long)b * g.sC + (long)row * g.ldc + n;
-        if (g.beta != 0.f) o += g.beta * *c;
-        *c = o;
-      }
+      const bool part = g.ksplit > 1;
+      store_c(part ? g.ws + ((long)split * g.batch + b) * (long)g.M * g.N + (long)row * g.N + n : nullptr,
+              g.C + (long)b * g.sC + (long)row * g.ldc + n, v, g.alpha,
+              (!part && g.bias) ? g.bias[(long)b * g.sBias + n] : 0.f, g.beta);
     }
   }
 }
 
+// (B with n contiguous is read as scalars: VB only exists with BKC)
 void launch_m16(const GemmArgs& g, bool bk, bool va, bool vb, hipStream_t st) {
   dim3 grid(sd_cdiv(g.N, 16), g.ksplit, g.batch);
-#define M16_L(B_, A_, V_) gemm_m16<B_, A_, V_><<<grid, 512, 0, st>>>(g)
-  if (bk) {
-    if (va && vb) M16_L(true, true, true); else if (va) M16_L(true, true, false);
-    else if (vb) M16_L(true, false, true); else M16_L(true, false, false);
-  } else {
-    if (va) M16_L(false, true, false); else M16_L(false, false, false);
-  }
-#undef M16_L
+  with_bools([&](auto BKC, auto VA, auto VB) { gemm_m16<BKC(), VA(), BKC() && VB()><<<grid, 512, 0, st>>>(g); },
+             bk, va, vb);
 }
 
 void launch_skinny(const GemmArgs& g, bool bk, bool va, bool vb, hipStream_t st) {
   dim3 grid(sd_cdiv(g.N, 32), g.ksplit, g.batch);
-#define SK_L(B_, A_, V_) gemm_skinny<B_, A_, V_><<<grid, 256, 0, st>>>(g)
-  if (bk) {
-    if (va && vb) SK_L(true, true, true); else if (va) SK_L(true, true, false);
-    else if (vb) SK_L(true, false, true); else SK_L(true, false, false);
-  } else {
-    if (va) SK_L(false, true, false); else SK_L(false, false, false);
-  }
-#undef SK_L
+  with_bools([&](auto BKC, auto VA, auto VB) { gemm_skinny<BKC(), VA(), BKC() && VB()><<<grid, 256, 0, st>>>(g); },
+             bk, va, vb);
 }
 
 }  // namespace
@@ -232,12 +185,8 @@ extern "C" int sd_gemm_f32(const sd_gemm_desc* d, float* workspace, long workspa
   hipStream_t stream = (hipStream_t)stream_;
   if (!d || !d->A || !d->B || !d->C) return SD_EARG;
   if (d->M <= 0 || d->N <= 0 || d->batch <= 0) return SD_OK;
-  GemmArgs g{};
-  g.A = d->A; g.B = d->B; g.C = d->C; g.bias = d->bias; g.ws = workspace;
-  g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc;
-  g.sA = d->strideA; g.sB = d->strideB; g.sC = d->strideC; g.sBias = d->strideBias;
-  g.M = d->M; g.N = d->N; g.K = d->K; g.batch = d->batch;
-  g.alpha = d->alpha; g.beta = d->beta;
+  GemmArgs g = args_from_desc(*d);
+  g.ws = workspace;
   int ks = d->ksplit < 1 ? 1 : d->ksplit;
   if (d->K <= 0) ks = 1;
   if (ks > 1 && (!workspace || workspace_floats < (long)ks * d->batch * d->M * d->N)) return SD_EARG;
@@ -249,17 +198,13 @@ extern "C" int sd_gemm_f32(const sd_gemm_desc* d, float* workspace, long workspa
   kc = (kc + kgran - 1) / kgran * kgran;
   g.kchunk = (int)kc;
   const bool ak = d->a_kcontig != 0, bk = d->b_kcontig != 0;
-  // float4 staging needs 16-B aligned bases, ld % 4 == 0 and batch strides % 4 == 0
-  const bool va = aligned16(d->A) && d->lda % 4 == 0 && (d->batch == 1 || d->strideA % 4 == 0);
-  const bool vb = aligned16(d->B) && d->ldb % 4 == 0 && (d->batch == 1 || d->strideB % 4 == 0);
+  const bool va = vec_ok(d->A, d->lda, d->batch, d->strideA), vb = vec_ok(d->B, d->ldb, d->batch, d->strideB);
   if (skinny) {
     if (m16) launch_m16(g, bk, va, vb, stream);
     else launch_skinny(g, bk, va, vb, stream);
     SD_LAUNCH_CHECK();
     if (ks > 1) {
-      long total = (long)d->batch * d->M * d->N;
-      int blocks = (int)((total + 255) / 256);
-      gemm_reduce_kernel<<<blocks, 256, 0, stream>>>(g);
+      launch_reduce(g, stream, false);
       SD_LAUNCH_CHECK();
     }
     return SD_OK;
@@ -271,16 +216,10 @@ extern "C" int sd_gemm_f32(const sd_gemm_desc* d, float* workspace, long workspa
     else if (tiles128 >= 256) tile = 0;
     else tile = 1;
   }
-  if (ak && bk) launch_layout<true, true>(g, tile, va, vb, stream);
-  else if (ak) launch_layout<true, false>(g, tile, va, vb, stream);
-  else if (bk) launch_layout<false, true>(g, tile, va, vb, stream);
-  else launch_layout<false, false>(g, tile, va, vb, stream);
+  with_bools([&](auto AK, auto BKC) { launch_layout<AK(), BKC()>(g, tile, va, vb, stream); }, ak, bk);
   SD_LAUNCH_CHECK();
   if (ks > 1) {
-    long total = (long)d->batch * d->M * d->N;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    gemm_reduce_kernel<<<blocks, 256, 0, stream>>>(g);
+    launch_reduce(g, stream, true);
     SD_LAUNCH_CHECK();
   }
   return SD_OK;

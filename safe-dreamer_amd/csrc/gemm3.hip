@@ -76,25 +76,18 @@ __global__ __launch_bounds__(256, (BM >= 256 ? 1 : 2)) void gemm3_kernel(GemmArg
   } else {
     gemm3_mainloop<BM, BN, WM, WN>(la, lb, kbeg, kend, acc);
   }
-  gemm3_epilogue<BM, BN, WM, WN>(g, acc, bm0, bn0, b, split);
+  sdg::epilogue16<BM, BN, WM, WN>(g, acc, bm0, bn0, b, split);
 }
 
 template <int BM, int BN, int WM, int WN, bool AK, bool BKC>
 void launch3_tile(const GemmArgs& g, bool va, bool vb, hipStream_t st) {
   dim3 grid(sd_cdiv(g.N, BN), sd_cdiv(g.M, BM), g.batch * g.ksplit);
-  if constexpr (!AK) {
-    if (g.rowsum) {
-      if (va && vb) gemm3_kernel<BM, BN, WM, WN, AK, BKC, true, true, true><<<grid, 256, 0, st>>>(g);
-      else if (va) gemm3_kernel<BM, BN, WM, WN, AK, BKC, true, false, true><<<grid, 256, 0, st>>>(g);
-      else if (vb) gemm3_kernel<BM, BN, WM, WN, AK, BKC, false, true, true><<<grid, 256, 0, st>>>(g);
-      else gemm3_kernel<BM, BN, WM, WN, AK, BKC, false, false, true><<<grid, 256, 0, st>>>(g);
-      return;
-    }
-  }
-  if (va && vb) gemm3_kernel<BM, BN, WM, WN, AK, BKC, true, true><<<grid, 256, 0, st>>>(g);
-  else if (va) gemm3_kernel<BM, BN, WM, WN, AK, BKC, true, false><<<grid, 256, 0, st>>>(g);
-  else if (vb) gemm3_kernel<BM, BN, WM, WN, AK, BKC, false, true><<<grid, 256, 0, st>>>(g);
-  else gemm3_kernel<BM, BN, WM, WN, AK, BKC, false, false><<<grid, 256, 0, st>>>(g);
+  // (row sums only with the rows-contiguous A loader; the entries that pass a rowsum admit no other)
+  sdg::with_bools(
+      [&](auto VA, auto VB, auto RS) {
+        gemm3_kernel<BM, BN, WM, WN, AK, BKC, VA(), VB(), !AK && RS()><<<grid, 256, 0, st>>>(g);
+      },
+      va, vb, g.rowsum != nullptr);
 }
 
 template <bool AK, bool BKC>
@@ -104,7 +97,8 @@ void launch3_layout(const GemmArgs& g, int tile, bool va, bool vb, hipStream_t s
   else launch3_tile<64, 64, 32, 32, AK, BKC>(g, va, vb, st);
 }
 
-bool al16_3(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using sdg::aligned16;
+using sdg::vec_ok;
 
 // ---- MLP layer on the split-bf16 core (sd_gemm_bf16x3_mlp): C[b] = act(rms(A[b]) * nw[b]) . B[b] + bias[b], the
 // RMSNorm (nn.RMSNorm, eps) + SiLU of the previous layer applied to A rows while they are staged into LDS (rstd from
@@ -415,12 +409,11 @@ extern "C" int sd_gemm_bf16x3_mlp(const sd_gemm_desc* d, const sd_mlp_ext* x, sd
   if (d->M <= 0 || d->N <= 0 || d->batch <= 0) return SD_OK;
   // the fused path's shapes: k-contiguous A and B (C = A . W^T), 16-B aligned, whole 32-deep k tiles, no split-K
   if (!d->a_kcontig || !d->b_kcontig || d->K % BK || d->K < BK || d->N < 64 || d->beta != 0.f) return SD_ESHAPE;
-  if (!al16_3(d->A) || !al16_3(d->B) || d->lda % 4 || d->ldb % 4 || (d->batch > 1 && (d->strideA % 4 || d->strideB % 4)))
-    return SD_ESHAPE;
+  if (!vec_ok(d->A, d->lda, d->batch, d->strideA) || !vec_ok(d->B, d->ldb, d->batch, d->strideB)) return SD_ESHAPE;
   bool any_nw = false;
   for (int b = 0; b < SD_MLP_MAXB && b < d->batch; ++b) any_nw = any_nw || x->norm_w_ptr[b];
   const bool rms = x->norm_w != nullptr || any_nw, pout = x->part_out != nullptr;
-  if (rms && (!x->part_in || x->npart_in <= 0 || (x->norm_w && (!al16_3(x->norm_w) || x->stride_norm_w % 4))))
+  if (rms && (!x->part_in || x->npart_in <= 0 || (x->norm_w && (!aligned16(x->norm_w) || x->stride_norm_w % 4))))
     return SD_EARG;
   if (rms && !x->norm_w)  // every entry needs its own norm weight then
     for (int b = 0; b < d->batch; ++b)
@@ -429,16 +422,13 @@ extern "C" int sd_gemm_bf16x3_mlp(const sd_gemm_desc* d, const sd_mlp_ext* x, sd
   bool per_entry = false;
   for (int b = 0; b < SD_MLP_MAXB; ++b) {
     if (x->w_rows[b] < 0 || x->w_rows[b] > d->N) return SD_EARG;
-    if ((x->w_ptr[b] && !al16_3(x->w_ptr[b])) || (x->norm_w_ptr[b] && !al16_3(x->norm_w_ptr[b]))) return SD_ESHAPE;
+    if ((x->w_ptr[b] && !aligned16(x->w_ptr[b])) || (x->norm_w_ptr[b] && !aligned16(x->norm_w_ptr[b])))
+      return SD_ESHAPE;
     per_entry = per_entry || x->w_ptr[b] || x->bias_ptr[b] || x->norm_w_ptr[b] || x->w_rows[b];
   }
   if (per_entry && d->batch > SD_MLP_MAXB) return SD_EARG;
-  GemmArgs g{};
-  g.A = d->A; g.B = d->B; g.C = d->C; g.bias = d->bias; g.ws = nullptr;
-  g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc;
-  g.sA = d->strideA; g.sB = d->strideB; g.sC = d->strideC; g.sBias = d->strideBias;
-  g.M = d->M; g.N = d->N; g.K = d->K; g.batch = d->batch;
-  g.alpha = d->alpha; g.beta = 0.f; g.ksplit = 1; g.kchunk = d->K;
+  GemmArgs g = sdg::args_from_desc(*d);  // (beta == 0 was checked above; no workspace)
+  g.ksplit = 1; g.kchunk = d->K;
   MlpExt e{x->norm_w, x->stride_norm_w, x->part_in, x->stride_part_in, x->npart_in, x->act, x->eps, x->part_out,
            x->stride_part_out, {}, {}, {}, {}};
   for (int b = 0; b < SD_MLP_MAXB; ++b) {
@@ -459,10 +449,7 @@ extern "C" int sd_gemm_bf16x3_mlp(const sd_gemm_desc* d, const sd_mlp_ext* x, sd
     return SD_OK;
   }
   const dim3 grid(sd_cdiv(g.N, 128), sd_cdiv(g.M, 128), g.batch);
-  if (rms && pout) gemm3_mlp_kernel<true, true><<<grid, 256, 0, st>>>(g, e);
-  else if (rms) gemm3_mlp_kernel<true, false><<<grid, 256, 0, st>>>(g, e);
-  else if (pout) gemm3_mlp_kernel<false, true><<<grid, 256, 0, st>>>(g, e);
-  else gemm3_mlp_kernel<false, false><<<grid, 256, 0, st>>>(g, e);
+  sdg::with_bools([&](auto RMS, auto POUT) { gemm3_mlp_kernel<RMS(), POUT()><<<grid, 256, 0, st>>>(g, e); }, rms, pout);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
@@ -504,17 +491,12 @@ constexpr long G3_T128 = 192;
 int gemm3_run(const sd_gemm_desc* d, float* workspace, long workspace_floats, float* rowsum, int rs_acc,
               sd_stream stream_, int rs_split, float* rowsum2) {
   hipStream_t stream = (hipStream_t)stream_;
-  GemmArgs g{};
+  GemmArgs g = sdg::args_from_desc(*d);
+  g.ws = workspace;
   g.rowsum = rowsum;
   g.rs_acc = rs_acc;
   g.rs_split = rs_split;
   g.rowsum2 = rowsum2;
-  g.rs_ws = nullptr;
-  g.A = d->A; g.B = d->B; g.C = d->C; g.bias = d->bias; g.ws = workspace;
-  g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc;
-  g.sA = d->strideA; g.sB = d->strideB; g.sC = d->strideC; g.sBias = d->strideBias;
-  g.M = d->M; g.N = d->N; g.K = d->K; g.batch = d->batch;
-  g.alpha = d->alpha; g.beta = d->beta;
   int ks = d->ksplit < 1 ? 1 : d->ksplit;
   const long slabs = (long)ks * d->batch * d->M * d->N;
   if (ks > 1 && (!workspace || workspace_floats < slabs + (rowsum ? (long)ks * d->M : 0))) return SD_EARG;
@@ -522,8 +504,7 @@ int gemm3_run(const sd_gemm_desc* d, float* workspace, long workspace_floats, fl
   g.ksplit = ks;
   long kc = ((long)d->K + ks - 1) / ks;
   g.kchunk = (int)((kc + BK - 1) / BK * BK);
-  const bool va = al16_3(d->A) && d->lda % 4 == 0 && (d->batch == 1 || d->strideA % 4 == 0);
-  const bool vb = al16_3(d->B) && d->ldb % 4 == 0 && (d->batch == 1 || d->strideB % 4 == 0);
+  const bool va = vec_ok(d->A, d->lda, d->batch, d->strideA), vb = vec_ok(d->B, d->ldb, d->batch, d->strideB);
   int tile = d->tile;
   const bool ak = d->a_kcontig != 0, bk = d->b_kcontig != 0;
   if (tile != 0 && tile != 1 && tile != 2) {
@@ -534,16 +515,10 @@ int gemm3_run(const sd_gemm_desc* d, float* workspace, long workspace_floats, fl
     tile = tiles128 >= G3_T128 ? 0 : 1;
   }
   if (tile == 2 && (ak || bk)) tile = 0;
-  if (ak && bk) launch3_layout<true, true>(g, tile, va, vb, stream);
-  else if (ak) launch3_layout<true, false>(g, tile, va, vb, stream);
-  else if (bk) launch3_layout<false, true>(g, tile, va, vb, stream);
-  else launch3_layout<false, false>(g, tile, va, vb, stream);
+  sdg::with_bools([&](auto AK, auto BKC) { launch3_layout<AK(), BKC()>(g, tile, va, vb, stream); }, ak, bk);
   SD_LAUNCH_CHECK();
   if (ks > 1) {
-    long total = (long)d->batch * d->M * d->N;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    sdg::gemm_reduce_kernel<<<blocks, 256, 0, stream>>>(g);
+    sdg::launch_reduce(g, stream, true);
     SD_LAUNCH_CHECK();
   }
   return SD_OK;

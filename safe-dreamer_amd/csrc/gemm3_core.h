@@ -22,10 +22,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 32;
-#ifndef SD_G3_PAD  // bf16 of padding per LDS row (A/B knob)
-#define SD_G3_PAD 8
-#endif
-constexpr int LROW = 2 * BK + SD_G3_PAD;  // bf16 per LDS row
+constexpr int LROW = 2 * BK + 8;  // bf16 per LDS row: hi | lo | 8 of padding (144-B rows, see above)
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -48,7 +45,9 @@ SD_DEV void split_store(__bf16* dst, f32x4 v) {
   *reinterpret_cast<bf16x4*>(dst + BK) = lo;
 }
 
-// Operand with k contiguous (row r, k at p[r * ld + k]): thread loads float4 runs along k.
+// Operand with k contiguous (row r, k at p[r * ld + k]): thread loads float4 runs along k. The same tile as the f32
+// core's TileLoader<ROWS, true, VEC>, written out: loading through that one (and through load4_guard) was measured
+// to cost the 64 x 64 kernel with an unvectorised A 3 %.
 template <int ROWS, bool VEC>
 struct KC3 {
   static constexpr int NV = (ROWS * BK / 4 + 255) / 256;
@@ -112,16 +111,7 @@ struct KM3 {
       for (int kk = 0; kk < 4; ++kk) {
         const int gk = k0 + 4 * kq + kk;
         f32x4 x = {0.f, 0.f, 0.f, 0.f};
-        if (i < NBLK && gk < kend) {
-          const float* q = p + (long)gk * ld + gr;
-          if (VEC && gr + 3 < nrows) {
-            x = *reinterpret_cast<const f32x4*>(q);
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              if (gr + j < nrows) x[j] = q[j];
-          }
-        }
+        if (i < NBLK && gk < kend) x = sdg::load4_guard<VEC>(p + (long)gk * ld + gr, gr, nrows);
         r[v][kk] = x;
       }
     }
@@ -242,51 +232,6 @@ SD_DEV void gemm3_mainloop(OpA& la, OpB& lb, int kbeg, int kend, f32x4 (&acc)[WM
     }
     __syncthreads();
   }
-}
-
-// C tile epilogue (alpha, bias, beta; or a split-K partial slab)
-template <int BM, int BN, int WM, int WN>
-SD_DEV void gemm3_epilogue(const GemmArgs& g, const f32x4 (&acc)[WM / 16][WN / 16], int bm0, int bn0, int b,
-                           int split) {
-  constexpr int WAVES_N = BN / WN;
-  constexpr int TM = WM / 16, TN = WN / 16;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave / WAVES_N, wc = wave % WAVES_N;
-  const int l16 = lane & 15, q = lane >> 4;
-  if (g.ksplit > 1) {
-    float* W = g.ws + ((long)split * g.batch + b) * (long)g.M * g.N;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = bn0 + wc * WN + 16 * j + l16;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = bm0 + wr * WM + 16 * i + 4 * q + r;
-          if (m < g.M && n < g.N) W[(long)m * g.N + n] = g.alpha * acc[i][j][r];
-        }
-      }
-    return;
-  }
-  float* C = g.C + (long)b * g.sC;
-  const float* bias = g.bias ? g.bias + (long)b * g.sBias : nullptr;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = bn0 + wc * WN + 16 * j + l16;
-      const float bv = (bias && n < g.N) ? bias[n] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = bm0 + wr * WM + 16 * i + 4 * q + r;
-        if (m < g.M && n < g.N) {
-          float v = g.alpha * acc[i][j][r] + bv;
-          float* c = C + (long)m * g.ldc + n;
-          if (g.beta != 0.f) v += g.beta * *c;
-          *c = v;
-        }
-      }
-    }
 }
 
 }  // namespace

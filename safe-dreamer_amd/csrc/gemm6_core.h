@@ -13,9 +13,9 @@
 // LDS image per operand tile: [row][a0 k0..31 | a1 k0..31 | a2 k0..31 | pad 16] bf16 = 224-B rows (56 dwords:
 // the 16 rows x 4 lane groups of a ds_read_b128 fragment read hit 64 distinct banks). MFMA operand per lane: row
 // l16, k = 8q .. 8q+7 (q = lane >> 4), one ds_read_b128 per plane; accumulator register r of a 16x16 tile holds
-// row 4q + r, column l16 (the layout of gemm16_mainloop_pf, so epilogues are shared).
+// row 4q + r, column l16 (the layout of gemm_core.h's gemm16 main loops, so epilogues are shared).
 //
-// Loaders are gemm16_mainloop_pf's (load(k0, kend) into registers) plus store6(__bf16*), which writes the three
+// Loaders are gemm16_mainloop_fp's (load(k0, kend) into registers) plus store6(__bf16*), which writes the three
 // planes of their BM/BN x 32 register tile (split3_store per float4).
 #pragma once
 #include "common.h"

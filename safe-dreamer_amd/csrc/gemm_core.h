@@ -1,8 +1,12 @@
 // Shared fp32-MFMA GEMM block core (see gemm.hip for the design notes). Operand "loaders" supply BK-deep
 // register tiles, so dense matrices (gemm.hip) and implicit-im2col convolution operands (conv.hip) share one
-// MFMA/LDS pipeline and one epilogue.
+// MFMA/LDS pipeline and one epilogue. The family's one guarded operand load (load4_guard), one C-element store
+// (store_c), one 16x16-tile epilogue (epilogue16) and the launchers' host glue (at the end) live here too.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
+#include "sdhip.h"
 
 namespace sdg {
 namespace {  // internal linkage: the core is instantiated per translation unit
@@ -35,6 +39,21 @@ SD_DEV float* rowsum_at(const GemmArgs& g, int m) {
   return (!g.rowsum2 || m < g.rs_split) ? g.rowsum + m : g.rowsum2 + (m - g.rs_split);
 }
 
+// q[0..3] are elements i .. i+3 of a dimension that ends at `end`: one float4 load when VEC (q is 16-B aligned) and
+// all four are inside, else four guarded scalars; elements past `end` read 0. The family's operand load (but KC3's).
+template <bool VEC>
+SD_DEV f32x4 load4_guard(const float* q, int i, int end) {
+  f32x4 x = {0.f, 0.f, 0.f, 0.f};
+  if (VEC && i + 3 < end) {
+    x = *reinterpret_cast<const f32x4*>(q);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (i + j < end) x[j] = q[j];
+  }
+  return x;
+}
+
 // Load a ROWS x BK tile of an operand into registers (rows = m for A / n for B).
 // KC: k contiguous (row-major in k, `ld` between rows) ; else rows contiguous (`ld` between k's).
 template <int ROWS, bool KC, bool VEC>
@@ -52,29 +71,11 @@ struct TileLoader {
         if (KC) {
           const int row = i / (BK / 4), kq = i % (BK / 4);
           const int gr = row0 + row, gk = k0 + 4 * kq;
-          if (gr < nrows) {
-            const float* q = p + (long)gr * ld + gk;
-            if (VEC && gk + 3 < kend) {
-              x = *reinterpret_cast<const f32x4*>(q);
-            } else {
-#pragma unroll
-              for (int j = 0; j < 4; ++j)
-                if (gk + j < kend) x[j] = q[j];
-            }
-          }
+          if (gr < nrows) x = load4_guard<VEC>(p + (long)gr * ld + gk, gk, kend);
         } else {
           const int k = i % BK, rq = i / BK;
           const int gk = k0 + k, gr = row0 + 4 * rq;
-          if (gk < kend) {
-            const float* q = p + (long)gk * ld + gr;
-            if (VEC && gr + 3 < nrows) {
-              x = *reinterpret_cast<const f32x4*>(q);
-            } else {
-#pragma unroll
-              for (int j = 0; j < 4; ++j)
-                if (gr + j < nrows) x[j] = q[j];
-            }
-          }
+          if (gk < kend) x = load4_guard<VEC>(p + (long)gk * ld + gr, gr, nrows);
         }
       }
       r[v] = x;
@@ -112,6 +113,18 @@ struct DenseOperand {
   SD_DEV void load(int k0, int kend) { t.load(p, ld, row0, nrows, k0, kend); }
   SD_DEV void store(float* lds) const { t.store(lds); }
 };
+
+// One C element from its accumulator: the split-K partial alpha * acc into `slab` when that is non-null (bias and
+// beta are the reduce kernel's then), else *c = alpha * acc + bv (+ beta * *c). bv is the caller's bias value or 0.
+SD_DEV void store_c(float* slab, float* c, float acc, float alpha, float bv, float beta) {
+  if (slab) {
+    *slab = alpha * acc;
+  } else {
+    float v = alpha * acc + bv;
+    if (beta != 0.f) v += beta * *c;
+    *c = v;
+  }
+}
 
 template <int BM, int BN, int WM, int WN, class OpA, class OpB>
 SD_DEV void gemm_block(const GemmArgs& g, OpA& la, OpB& lb, int bm0, int bn0, int b, int split, int kbeg, int kend) {
@@ -194,7 +207,7 @@ SD_DEV void gemm_block(const GemmArgs& g, OpA& la, OpB& lb, int bm0, int bn0, in
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int m = bm0 + wr * WM + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-          if (m < g.M && n < g.N) W[(long)m * g.N + n] = g.alpha * acc[i][j][r];
+          if (m < g.M && n < g.N) store_c(W + (long)m * g.N + n, nullptr, acc[i][j][r], g.alpha, 0.f, 0.f);
         }
       }
     return;
@@ -210,12 +223,7 @@ SD_DEV void gemm_block(const GemmArgs& g, OpA& la, OpB& lb, int bm0, int bn0, in
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = bm0 + wr * WM + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (m < g.M && n < g.N) {
-          float v = g.alpha * acc[i][j][r] + bv;
-          float* c = C + (long)m * g.ldc + n;
-          if (g.beta != 0.f) v += g.beta * *c;
-          *c = v;
-        }
+        if (m < g.M && n < g.N) store_c(nullptr, C + (long)m * g.ldc + n, acc[i][j][r], g.alpha, bv, g.beta);
       }
     }
 }
@@ -262,16 +270,7 @@ struct DenseKM : KMajor<ROWS> {
       const int i = threadIdx.x + v * 256;
       f32x4 x = {0.f, 0.f, 0.f, 0.f};
       const int gk = k0 + this->kk(i), gr = row0 + 4 * this->rq(i);
-      if (i < ROWS * BK / 4 && gk < kend) {
-        const float* q = p + (long)gk * ld + gr;
-        if (VEC && gr + 3 < nrows) {
-          x = *reinterpret_cast<const f32x4*>(q);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (gr + j < nrows) x[j] = q[j];
-        }
-      }
+      if (i < ROWS * BK / 4 && gk < kend) x = load4_guard<VEC>(p + (long)gk * ld + gr, gr, nrows);
       r[v] = x;
     }
   }
@@ -286,27 +285,24 @@ struct is_kmajor { static constexpr bool value = false; };
 template <class Op>
 struct is_kmajor<Op, decltype(void(Op::KMAJOR))> { static constexpr bool value = Op::KMAJOR; };
 
-// PF = K-tiles in flight in registers (loader copies la[PF] / lb[PF]); the LDS image is double-buffered. With PF > 1
-// a tile's global loads are issued PF iterations before its LDS store, hiding L2 latency behind PF tiles of MFMA work
-// when a launch has too few waves per SIMD to hide it by occupancy. The k loop is unrolled by PF so every register
-// set is statically indexed.
 // Static LDS block of N floats, one per (kernel, N): lets an epilogue reuse a main loop's staging area.
 template <int N>
 SD_DEV float* sd_smem() {
   __shared__ __attribute__((aligned(16))) float s[N];
   return s;
 }
-// floats of gemm16_mainloop_pf's double-buffered staging area
+// floats of gemm16_mainloop's double-buffered staging area
 template <int BM, int BN, bool AKM = false, bool BKM = false>
 constexpr int gemm16_smem_floats() {
   return 2 * ((AKM ? BK * (BM + 2) : BM * LDS_ROW) + (BKM ? BK * (BN + 2) : BN * LDS_ROW));
 }
 
-// ES (early store): stage tile kt+1 and issue the loads of tile kt+1+PF BEFORE this tile's MFMAs (after its fragment
-// reads), so the loads' address arithmetic fills the MFMA issue gaps; otherwise after them.
-template <int BM, int BN, int WM, int WN, int PF = 1, bool ES = false, class OpA, class OpB>
-SD_DEV void gemm16_mainloop_pf(OpA (&la)[PF], OpB (&lb)[PF], int kbeg, int kend, f32x4 (&acc)[WM / 16][WN / 16],
-                               bool accumulate = false) {
+// acc (+)= A . B^T over [kbeg, kend): one k tile ahead in registers, the LDS image double-buffered. Iteration kt
+// reads its fragments from LDS[kt & 1], runs its MFMAs, then stages tile kt+1 (loaded one iteration earlier) into the
+// other buffer and issues the loads of tile kt+2; one barrier per k tile.
+template <int BM, int BN, int WM, int WN, class OpA, class OpB>
+SD_DEV void gemm16_mainloop(OpA& la, OpB& lb, int kbeg, int kend, f32x4 (&acc)[WM / 16][WN / 16],
+                            bool accumulate = false) {
   constexpr int WAVES_N = BN / WN;
   constexpr int TM = WM / 16, TN = WN / 16;
   static_assert((BM / WM) * (BN / WN) == 4, "4 waves");
@@ -339,17 +335,14 @@ SD_DEV void gemm16_mainloop_pf(OpA (&la)[PF], OpB (&lb)[PF], int kbeg, int kend,
   // the steady-state body issues every load unconditionally: a load under a branch makes hipcc drain vmcnt(0) at
   // the merge, which would serialise the whole prefetch pipeline
   auto ktile = [&](int t) { return kbeg + (t < nk ? t : nk - 1) * BK; };
-#pragma unroll
-  for (int u = 0; u < PF; ++u) {
-    la[u].load(ktile(u), kend);
-    lb[u].load(ktile(u), kend);
-  }
-  la[0].store(smem);
-  lb[0].store(smem + SA);
+  la.load(ktile(0), kend);
+  lb.load(ktile(0), kend);
+  la.store(smem);
+  lb.store(smem + SA);
   __syncthreads();
-  la[0].load(ktile(PF), kend);
-  lb[0].load(ktile(PF), kend);
-  auto step = [&](int kt, int u) {
+  la.load(ktile(1), kend);
+  lb.load(ktile(1), kend);
+  for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
     float af[TM][8], bf[TN][8];
 #pragma unroll
@@ -380,14 +373,6 @@ SD_DEV void gemm16_mainloop_pf(OpA (&la)[PF], OpB (&lb)[PF], int kbeg, int kend,
         for (int s = 0; s < 4; ++s) { bf[j][s] = x0[s]; bf[j][4 + s] = x1[s]; }
       }
     }
-    // tile kt+1 lives in register set (u+1) % PF: stage it, then refill that set with tile kt+1+PF
-    const int nx = (u + 1) % PF;  // static after unrolling
-    if constexpr (ES) {
-      la[nx].store(smem + (cur ^ 1) * STAGE);
-      lb[nx].store(smem + (cur ^ 1) * STAGE + SA);
-      la[nx].load(ktile(kt + 1 + PF), kend);
-      lb[nx].load(ktile(kt + 1 + PF), kend);
-    }
 #pragma unroll
     for (int s = 0; s < 8; ++s)
 #pragma unroll
@@ -399,27 +384,15 @@ SD_DEV void gemm16_mainloop_pf(OpA (&la)[PF], OpB (&lb)[PF], int kbeg, int kend,
           else
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][s], bf[j][s], acc[i][j], 0, 0, 0);
         }
-    if constexpr (!ES) {
-      // keep the LDS store of the next tile behind this tile's MFMAs: hoisted into them, its vmcnt(0) wait would
-      // cut the window in which the global loads land from the whole k tile to a few MFMAs
-#ifndef SD_NO_SCHED_BARRIER
-      __builtin_amdgcn_sched_barrier(0);
-#endif
-      la[nx].store(smem + (cur ^ 1) * STAGE);
-      lb[nx].store(smem + (cur ^ 1) * STAGE + SA);
-      la[nx].load(ktile(kt + 1 + PF), kend);
-      lb[nx].load(ktile(kt + 1 + PF), kend);
-    }
+    // keep the LDS store of the next tile behind this tile's MFMAs: hoisted into them, its vmcnt(0) wait would
+    // cut the window in which the global loads land from the whole k tile to a few MFMAs
+    __builtin_amdgcn_sched_barrier(0);
+    la.store(smem + (cur ^ 1) * STAGE);
+    lb.store(smem + (cur ^ 1) * STAGE + SA);
+    la.load(ktile(kt + 2), kend);
+    lb.load(ktile(kt + 2), kend);
     __syncthreads();
-  };
-  int kt = 0;
-  for (; kt + PF <= nk; kt += PF) {
-#pragma unroll
-    for (int u = 0; u < PF; ++u) step(kt + u, u);
   }
-#pragma unroll
-  for (int u = 0; u < PF; ++u)
-    if (kt + u < nk) step(kt + u, u);
   if (XC == 2) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -428,11 +401,12 @@ SD_DEV void gemm16_mainloop_pf(OpA (&la)[PF], OpB (&lb)[PF], int kbeg, int kend,
   }
 }
 
-// Fragment-prefetch variant of gemm16_mainloop_pf (row-major LDS operands): iteration kt issues the LDS fragment
+// Fragment-prefetch variant of gemm16_mainloop (row-major LDS operands): iteration kt issues the LDS fragment
 // reads of tile kt+1 BEFORE its own MFMAs, which run on fragments read one iteration earlier, so the LDS latency sits
 // under the MFMAs instead of in front of them; the MFMA pipe only idles over the next tile's store and the barrier.
 // Two LDS stages suffice: iteration kt stores tile kt+2 into stage kt&1, whose tile-kt fragments every wave read
-// before iteration kt-1's barrier. Register tile t lives in set t % PF as in gemm16_mainloop_pf.
+// before iteration kt-1's barrier. PF k tiles are in flight in registers (loader copies la[PF] / lb[PF]): register
+// tile t lives in set t % PF, and the k loop is unrolled by PF so every set is statically indexed.
 template <int BM, int BN, int WM, int WN, int PF = 1, class OpA, class OpB>
 SD_DEV void gemm16_mainloop_fp(OpA (&la)[PF], OpB (&lb)[PF], int kbeg, int kend, f32x4 (&acc)[WM / 16][WN / 16],
                                bool accumulate = false) {
@@ -595,28 +569,16 @@ SD_DEV void gemm16_mainloop_es(OpA& la, OpB& lb, int kbeg, int kend, f32x4 (&acc
   }
 }
 
-template <int BM, int BN, int WM, int WN, class OpA, class OpB>
-SD_DEV void gemm16_mainloop(OpA& la, OpB& lb, int kbeg, int kend, f32x4 (&acc)[WM / 16][WN / 16]) {
-  OpA (&a1)[1] = *reinterpret_cast<OpA(*)[1]>(&la);
-  OpB (&b1)[1] = *reinterpret_cast<OpB(*)[1]>(&lb);
-  gemm16_mainloop_pf<BM, BN, WM, WN, 1>(a1, b1, kbeg, kend, acc);
-}
-
-template <int BM, int BN, int WM, int WN, bool ES = false, class OpA, class OpB>
-SD_DEV void gemm_block16(const GemmArgs& g, OpA& la, OpB& lb, int bm0, int bn0, int b, int split, int kbeg,
-                         int kend) {
+// C tile epilogue of the 16x16-MFMA main loops, f32 and split-bf16 (alpha, bias, beta; or a split-K partial slab):
+// reg r of a 16x16 tile -> row 4q + r, col l16. The slab and the final case keep a loop nest each: folded into one,
+// the choice lands in the inner loop and the 128-row split-bf16 kernels' register budget moves.
+template <int BM, int BN, int WM, int WN>
+SD_DEV void epilogue16(const GemmArgs& g, const f32x4 (&acc)[WM / 16][WN / 16], int bm0, int bn0, int b, int split) {
   constexpr int WAVES_N = BN / WN;
   constexpr int TM = WM / 16, TN = WN / 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave / WAVES_N, wc = wave % WAVES_N;
   const int l16 = lane & 15, q = lane >> 4;
-  f32x4 acc[TM][TN];
-  if constexpr (ES)
-    gemm16_mainloop_es<BM, BN, WM, WN>(la, lb, kbeg, kend, acc);
-  else
-    gemm16_mainloop<BM, BN, WM, WN>(la, lb, kbeg, kend, acc);
-
-  // epilogue: reg r of a 16x16 tile -> row 4q + r, col l16
   if (g.ksplit > 1) {
     float* W = g.ws + ((long)split * g.batch + b) * (long)g.M * g.N;
 #pragma unroll
@@ -627,7 +589,7 @@ SD_DEV void gemm_block16(const GemmArgs& g, OpA& la, OpB& lb, int bm0, int bn0, 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int m = bm0 + wr * WM + 16 * i + 4 * q + r;
-          if (m < g.M && n < g.N) W[(long)m * g.N + n] = g.alpha * acc[i][j][r];
+          if (m < g.M && n < g.N) store_c(W + (long)m * g.N + n, nullptr, acc[i][j][r], g.alpha, 0.f, 0.f);
         }
       }
     return;
@@ -643,14 +605,20 @@ SD_DEV void gemm_block16(const GemmArgs& g, OpA& la, OpB& lb, int bm0, int bn0, 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = bm0 + wr * WM + 16 * i + 4 * q + r;
-        if (m < g.M && n < g.N) {
-          float v = g.alpha * acc[i][j][r] + bv;
-          float* c = C + (long)m * g.ldc + n;
-          if (g.beta != 0.f) v += g.beta * *c;
-          *c = v;
-        }
+        if (m < g.M && n < g.N) store_c(nullptr, C + (long)m * g.ldc + n, acc[i][j][r], g.alpha, bv, g.beta);
       }
     }
+}
+
+template <int BM, int BN, int WM, int WN, bool ES = false, class OpA, class OpB>
+SD_DEV void gemm_block16(const GemmArgs& g, OpA& la, OpB& lb, int bm0, int bn0, int b, int split, int kbeg,
+                         int kend) {
+  f32x4 acc[WM / 16][WN / 16];
+  if constexpr (ES)
+    gemm16_mainloop_es<BM, BN, WM, WN>(la, lb, kbeg, kend, acc);
+  else
+    gemm16_mainloop<BM, BN, WM, WN>(la, lb, kbeg, kend, acc);
+  epilogue16<BM, BN, WM, WN>(g, acc, bm0, bn0, b, split);
 }
 
 template <int BM, int BN, int WM, int WN, bool AK, bool BKC, bool VA, bool VB>
@@ -686,6 +654,44 @@ __global__ void gemm_reduce_kernel(GemmArgs g) {
       *o = (g.rs_acc ? *o : 0.f) + g.alpha * v;
     }
   }
+}
+
+// ---------------------------------------------------------------- host glue shared by the launchers
+// The descriptor's operands, shape and scaling; the caller sets ws, ksplit, kchunk (and the row-sum fields).
+GemmArgs args_from_desc(const sd_gemm_desc& d) {
+  GemmArgs g{};
+  g.A = d.A; g.B = d.B; g.C = d.C; g.bias = d.bias;
+  g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc;
+  g.sA = d.strideA; g.sB = d.strideB; g.sC = d.strideC; g.sBias = d.strideBias;
+  g.M = d.M; g.N = d.N; g.K = d.K; g.batch = d.batch;
+  g.alpha = d.alpha; g.beta = d.beta;
+  return g;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// float4 staging of an operand needs a 16-B aligned base, ld % 4 == 0 and a batch stride % 4 == 0
+bool vec_ok(const void* p, long ld, int batch, long stride) {
+  return aligned16(p) && ld % 4 == 0 && (batch == 1 || stride % 4 == 0);
+}
+
+// Sums a split-K launch's slabs (and row-sum partials) into C; cap: at most 4096 blocks, grid-strided. The caller
+// checks the launch.
+void launch_reduce(const GemmArgs& g, hipStream_t st, bool cap) {
+  const long total = (long)g.batch * g.M * g.N;
+  int blocks = (int)((total + 255) / 256);
+  if (cap && blocks > 4096) blocks = 4096;
+  gemm_reduce_kernel<<<blocks, 256, 0, st>>>(g);
+}
+
+// f(std::bool_constant...) with each runtime bool as a compile-time one, so f can use them as template arguments
+template <class F>
+void with_bools(F&& f) {
+  f();
+}
+template <class F, class... Bs>
+void with_bools(F&& f, bool b, Bs... bs) {
+  if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, bs...);
+  else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, bs...);
 }
 
 

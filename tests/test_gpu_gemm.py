@@ -53,6 +53,52 @@ def test_gemm_skinny(M, N, K, bk):
     assert (out.double() - ref).abs().max().item() < 2e-6 * (a.abs().double() @ w.abs().double().t()).max().item() + 1e-5
 
 
+@pytest.mark.parametrize("M,N,K", [(130, 70, 37), (128, 64, 64)])
+@pytest.mark.parametrize("ak", [True, False])
+@pytest.mark.parametrize("bk", [True, False])
+@pytest.mark.parametrize("ks", [1, 3])
+def test_gemm_f32_tile3(M, N, K, ak, bk, ks):
+    """The f32 128 x 64 tile, which only an explicit tile = 3 launches: pre-filled out, bias and beta = 1, every
+    layout, with and without split-K. (130, 70, 37) is ragged in every dimension and K % 4 != 0 (no leading dimension
+    is a multiple of 4: the unvectorised loaders); (128, 64, 64) is one whole tile on the float4 loaders."""
+    from sdreamer import kernels as k
+    g = torch.Generator(device="cpu").manual_seed(M * 7 + N * 3 + K)
+    a0 = torch.randn(M, K, generator=g).to("cuda")
+    b0 = torch.randn(K, N, generator=g).to("cuda")
+    a = a0 if ak else a0.t().contiguous().t()
+    b = b0.t().contiguous().t() if bk else b0
+    bias = torch.randn(N, generator=g).to("cuda")
+    c0 = torch.randn(M, N, generator=g).to("cuda")
+    out = c0.clone()
+    k.gemm(a, b, out, bias=bias, beta=1.0, tile=3, ksplit=ks)
+    err = (out.double() - _ref(a0, b0, bias, c0, beta=1.0)).abs().max().item()
+    assert err <= 2e-6 * (a0.double().abs() @ b0.double().abs()).max().item(), err
+
+
+@pytest.mark.parametrize("ks", [1, 3])
+@pytest.mark.parametrize("fused_db", [False, True])
+def test_gemm_bf16x3_tile2(ks, fused_db):
+    """The split-bf16 256 x 128 tile, which only an explicit tile = 2 launches (rows-contiguous A and B: a weight
+    gradient dw += dy^T x): (M, N, K) = (257, 130, 96) has a ragged second row tile and one 32-deep k tile per split
+    at ks = 3; with the fused bias gradient (rowsum) and without, db checked as test_wgrad_fused_bias does."""
+    from sdreamer import kernels as k
+    M, N, K = 257, 130, 96
+    g = torch.Generator().manual_seed(M + N + K)
+    dy = torch.randn(K, M, generator=g)
+    x = torch.randn(K, N, generator=g)
+    dw0 = torch.randn(M, N, generator=g)
+    db0 = torch.randn(M, generator=g)
+    dw, db = dw0.clone().to("cuda"), db0.clone().to("cuda")
+    ok = k.gemm(dy.to("cuda").t(), x.to("cuda"), dw, beta=1.0, fast=True, tile=2, ksplit=ks,
+                rowsum=db if fused_db else None)
+    assert ok is not False
+    ref = dw0.double() + dy.double().t() @ x.double()
+    bound = (dy.abs().double().t() @ x.abs().double()) * 4e-5 + 1e-5
+    assert ((dw.double().cpu() - ref).abs() <= bound).all()
+    dref = db0.double() + (dy.double().sum(0) if fused_db else 0)
+    assert torch.allclose(db.double().cpu(), dref, rtol=1e-5, atol=1e-4 * float(dy.abs().sum(0).max()) * 1e-2)
+
+
 def test_colsum_long():
     from sdreamer import kernels as k
     g = torch.Generator(device="cpu").manual_seed(3)
