@@ -851,33 +851,247 @@ __global__ __launch_bounds__(256, OCC) void conv_fwd_direct_pool_c4(GemmArgs g, 
 // its halo ((R+kh-1) x (W+kw-1) x Ci, zero padded) — and runs every (co, j) product of that block from LDS, so the
 // 25x im2col expansion is never read from memory (one patch read per row block instead of one per tap).
 // Wave w owns NBW 16-column blocks of j, all TM 16-row blocks of co: acc = TM*NBW 16x16 fp32 tiles in registers,
-// accumulated over the row blocks blockIdx.y, +gridDim.y, ...; the gridDim.y partial slabs are summed by
-// gemm_reduce_kernel. MFMA 16x16x4: lane (l16, q) supplies dy[p = 4s+q][co = l16] and x-patch[p = 4s+q][j = l16].
-// LDS row strides are padded to 16 (mod 64) floats so the 4 lane groups hit distinct banks.
+// accumulated over the row blocks blockIdx.y, +gridDim.y, ...; the gridDim.y partial slabs are summed by slab_reduce.
+// One skeleton (wgrad_direct_body) on two math paths, WdF32 and WdBf16x3: a path keeps its LDS layout and one-time
+// initialisation, its dy fetch registers and stage, its patch stage and the contraction over a staged block.
 struct DirectW {
   const float* x;
   const float* dy;      // (Nb, H, W, Co) conv-output gradient, or (PL) the pooled-resolution gradient (Nb, H/2, W/2, Co)
   const uint8_t* amax;  // PL: the 2x2 max-pool argmax per pooled element (dy is routed to that window position)
   float* ws;
   int Nb, H, W, Ci, Co, kh, kw, pad, R, lw;  // lw = log2(W)
-  int J, PW, PH, SA, CP, blocks;
+  int J, PW, PH, CP, DS, blocks;  // DS: stride of the staged dy (f32: floats per pixel; split-bf16: bf16 per channel)
 };
 
-SD_DEV int pad16(int c) { return c % 32 == 0 ? c + 16 : c; }
+constexpr int WD_VA = 4, WD_VP = 6;  // max float4 per thread of a staged dy block (f32 path) / input patch
 
-constexpr int WD_VA = 4, WD_VP = 6;  // max float4 per thread of a staged dy block / input patch
+// The f32 path. MFMA 16x16x4: lane (l16, q) supplies dy[p = 4s+q][co = l16] and x-patch[p = 4s+q][j = l16].
+// LDS row strides are padded to 16 (mod 64) floats so the 4 lane groups hit distinct banks.
+template <int TM, bool PL>
+struct WdF32 {
+  const DirectW& d;
+  const int tid, nA;
+  float* const dyl;  // [P][DS]
+  float* const xp;   // [PH][PW][CP]; channel Ci holds 1.0 (bias column), Ci+1 holds 0.0
+  f32x4 ra[WD_VA];
+  uint32_t aa[PL ? WD_VA : 1];
+  SD_DEV WdF32(const DirectW& d_, float* lds, int tid_)
+      : d(d_), tid(tid_), nA(d_.R * d_.W * d_.Co / 4), dyl(lds), xp(lds + d_.R * d_.W * d_.DS) {}
+  SD_DEV void init() {  // the constant channels never change: write them once
+    for (int pix = tid; pix < d.PH * d.PW; pix += 512) {
+      xp[pix * d.CP + d.Ci] = 1.f;
+      xp[pix * d.CP + d.Ci + 1] = 0.f;
+    }
+  }
+  SD_DEV void fetch_dy(int n, int y0) {
+    const float* dsrc = d.dy + ((long)n * d.H + y0) * d.W * d.Co;
+#pragma unroll
+    for (int v = 0; v < WD_VA; ++v) {
+      const int i = tid + 512 * v;
+      if constexpr (PL) {  // item i = (pooled pixel of the block, 4-channel group): raw gradient + argmax bytes
+        ra[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+        aa[v] = 0xffffffffu;
+        if (i < nA / 4) {
+          const long pp = (((long)n * (d.H >> 1) + (y0 >> 1)) * (d.W >> 1)) * d.Co + 4 * i;
+          ra[v] = *reinterpret_cast<const f32x4*>(d.dy + pp);
+          aa[v] = *reinterpret_cast<const uint32_t*>(d.amax + pp);
+        }
+      } else {
+        ra[v] = i < nA ? *reinterpret_cast<const f32x4*>(dsrc + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
+  SD_DEV void stage_dy() {
+#pragma unroll
+    for (int v = 0; v < WD_VA; ++v) {
+      const int i = tid + 512 * v;
+      if constexpr (PL) {  // route the pooled gradient to its argmax position of the 2x2 window, zeros elsewhere
+        if (i < nA / 4) {
+          const int e = 4 * i, pl = e / d.Co, c = e - pl * d.Co;
+          const int hw = d.W >> 1, pr = pl / hw, pc = pl - pr * hw;
+#pragma unroll
+          for (int qd = 0; qd < 4; ++qd) {
+            const int p = (2 * pr + (qd >> 1)) * d.W + 2 * pc + (qd & 1);
+            f32x4 val;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) val[k] = ((aa[v] >> (8 * k)) & 0xffu) == (uint32_t)qd ? ra[v][k] : 0.f;
+            *reinterpret_cast<f32x4*>(dyl + p * d.DS + c) = val;
+          }
+        }
+      } else if (i < nA) {
+        const int e = 4 * i, p = e / d.Co, c = e - p * d.Co;
+        *reinterpret_cast<f32x4*>(dyl + p * d.DS + c) = ra[v];
+      }
+    }
+  }
+  SD_DEV void stage_patch(int pix, int c, const f32x4& v) { *reinterpret_cast<f32x4*>(xp + pix * d.CP + c) = v; }
+  template <int NBW, bool WS>
+  SD_DEV void contract(f32x4 (&acc)[TM][NBW], const int (&off)[NBW], int P, int wave, int l16, int q) {
+    for (int s = WS ? wave : 0; s < P / 4; s += WS ? NW_D : 1) {
+      const int p = 4 * s + q, py = p >> d.lw, px = p & (d.W - 1);
+      float a[TM];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) a[i] = dyl[p * d.DS + 16 * i + l16];
+      const float* xb = xp + (py * d.PW + px) * d.CP;
+      float bv[NBW];
+#pragma unroll
+      for (int b = 0; b < NBW; ++b) bv[b] = xb[off[b]];
+#pragma unroll
+      for (int b = 0; b < NBW; ++b)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) acc[i][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], bv[b], acc[i][b], 0, 0, 0);
+    }
+  }
+};
 
-// WS (wave split): for narrow j ranges every wave covers all j blocks over every 8th k step and writes its own slab
-// PL: dy is the max-pool backward's input (pooled resolution + argmax), expanded while it is fetched — the
-// full-resolution conv gradient (3/4 zeros) is never written to or read from HBM.
-template <int TM, int NBW, bool WS, bool PL = false>
-__global__ __launch_bounds__(512) void conv_wgrad_direct(DirectW d) {
+SD_DEV uint32_t pack_split(float v) {  // (bf16 hi | bf16 lo << 16), hi + lo = v up to 2^-17 |v| (split2's values)
+  const f32x4 x = {v, 0.f, 0.f, 0.f};
+  sdb::bf16x4 hi, lo;
+  sdb::split2(x, hi, lo);
+  return (uint32_t)__builtin_bit_cast(uint16_t, hi[0]) | ((uint32_t)__builtin_bit_cast(uint16_t, lo[0]) << 16);
+}
+
+// The split-bf16 path, on v_mfma_f32_16x16x32_bf16 (~1e-5 relative, three products per step).
+// k = pixels, 32 per MFMA step: lane group q supplies pixels 4i + q (i = 0..7) of the step, so the 4 lane groups read
+// neighbouring pixels of the patch (CP floats apart: conflict-free) and each lane's 8 B-values are 8 ds_read_b32 at
+// precomputed pixel offsets + its column's tap offset. dy of the block is staged transposed and pre-split,
+// [co][pos] per plane with pos = 8 (p % 4) + (p / 4) % 8 inside each 32-pixel step, so a lane's 8 A-values (the same
+// pixels) are one ds_read_b128 per plane (rows >= Co read zero rows).
+// The input patch is staged PRE-SPLIT, each element as one 32-bit word (bf16 hi in the low half, bf16 lo in the high
+// half: the same split2 values), so the inner loop forms a lane's 8 B-values of each plane with 4 v_perm_b32. (The
+// first form staged f32 and re-split 8 floats per use, and every patch element feeds kh * kw taps x the column
+// blocks: bit-identical products, the split VALU moved from the k loop to the stage.)
+template <int TM, bool PL>
+struct WdBf16x3 {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const DirectW& d;
+  const int tid;
+  float* const xp;    // [PH][PW][CP] packed words; channel Ci holds 1.0 (bias column), Ci+1 holds 0.0
+  __bf16* const dyh;  // [TM*16][DS]
+  __bf16* const dyl;
+  // this thread's dy block: 4 channels x 4 pixels (pixels c + 4 (4 ih + t) of 32-pixel step sb, t = 0..3)
+  int nD, dq4, dc, dih, dsb;  // nD 4x4 blocks: 8 pixel groups per 32-pixel step
+  f32x4 rd[4];
+  uint32_t aw[PL ? 4 : 1];  // PL: the 4 channels' argmax bytes of each pixel's pooled element
+  int qd[PL ? 4 : 1];       // PL: the pixel's position in its 2x2 window
+  SD_DEV WdBf16x3(const DirectW& d_, float* lds, int tid_)
+      : d(d_), tid(tid_), xp(lds), dyh(reinterpret_cast<__bf16*>(lds + d_.PH * d_.PW * d_.CP)),
+        dyl(dyh + TM * 16 * d_.DS) {
+    for (int e = tid; e < TM * 16 * d.DS; e += 512) {  // rows >= Co stay zero; rows < Co are overwritten per block
+      dyh[e] = (__bf16)0.f;
+      dyl[e] = (__bf16)0.f;
+    }
+  }
+  SD_DEV void init() {  // the thread's dy block and the constant channels
+    const int c4 = d.Co / 4, drest = tid / c4;
+    nD = c4 * (d.R * d.W / 4);
+    dq4 = tid % c4;
+    dc = drest % 4, dih = (drest / 4) % 2, dsb = drest / 8;
+    for (int pix = tid; pix < d.PH * d.PW; pix += 512) {
+      reinterpret_cast<uint32_t*>(xp)[pix * d.CP + d.Ci] = pack_split(1.f);
+      reinterpret_cast<uint32_t*>(xp)[pix * d.CP + d.Ci + 1] = 0u;
+    }
+  }
+  SD_DEV void fetch_dy(int n, int y0) {
+    [[maybe_unused]] const float* dsrc = d.dy + ((long)n * d.H + y0) * d.W * d.Co;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int px = 32 * dsb + dc + 4 * (4 * dih + t);
+      if constexpr (PL) {  // the pooled element of pixel px (row y0 + px / W), loaded whole; masked in stage_dy()
+        const int yy = y0 + (px >> d.lw), xx = px & (d.W - 1);
+        const long pp = (((long)n * (d.H >> 1) + (yy >> 1)) * (d.W >> 1) + (xx >> 1)) * d.Co + 4 * dq4;
+        const bool ok = tid < nD;
+        rd[t] = ok ? *reinterpret_cast<const f32x4*>(d.dy + pp) : f32x4{0.f, 0.f, 0.f, 0.f};
+        aw[t] = ok ? *reinterpret_cast<const uint32_t*>(d.amax + pp) : 0xffffffffu;
+        qd[t] = (yy & 1) * 2 + (xx & 1);
+      } else {
+        rd[t] = tid < nD ? *reinterpret_cast<const f32x4*>(dsrc + (long)px * d.Co + 4 * dq4)
+                         : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
+  SD_DEV void stage_dy() {
+    if (tid < nD) {
+      const int pos = 32 * dsb + 8 * dc + 4 * dih;
+      if constexpr (PL) {  // route the pooled gradient to its argmax position of the 2x2 window, zeros elsewhere
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (((aw[t] >> (8 * k)) & 0xffu) != (uint32_t)qd[t]) rd[t][k] = 0.f;
+      }
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const f32x4 t = {rd[0][jj], rd[1][jj], rd[2][jj], rd[3][jj]};
+        sdb::bf16x4 hi, lo;
+        sdb::split2(t, hi, lo);
+        const int o = (4 * dq4 + jj) * d.DS + pos;
+        *reinterpret_cast<sdb::bf16x4*>(dyh + o) = hi;
+        *reinterpret_cast<sdb::bf16x4*>(dyl + o) = lo;
+      }
+    }
+  }
+  SD_DEV void stage_patch(int pix, int c, const f32x4& v) {
+    sdb::bf16x4 hi, lo;
+    sdb::split2(v, hi, lo);
+    const uint64_t h = __builtin_bit_cast(uint64_t, hi), l = __builtin_bit_cast(uint64_t, lo);
+    u32x4 w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = (uint32_t)((h >> (16 * k)) & 0xffffu) | ((uint32_t)((l >> (16 * k)) & 0xffffu) << 16);
+    *reinterpret_cast<u32x4*>(xp + pix * d.CP + c) = w;
+  }
+  template <int NBW, bool WS>
+  SD_DEV void contract(f32x4 (&acc)[TM][NBW], const int (&off)[NBW], int P, int wave, int l16, int q) {
+    for (int s = WS ? wave : 0; s < P / 32; s += WS ? NW_D : 1) {
+      sdb::bf16x8 ah[TM], al[TM];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int o = (16 * i + l16) * d.DS + 32 * s + 8 * q;
+        ah[i] = *reinterpret_cast<const sdb::bf16x8*>(dyh + o);
+        al[i] = *reinterpret_cast<const sdb::bf16x8*>(dyl + o);
+      }
+      int pb[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int p = 32 * s + 4 * i + q, py = p >> d.lw, px = p & (d.W - 1);
+        pb[i] = (py * d.PW + px) * d.CP;
+      }
+#pragma unroll
+      for (int b = 0; b < NBW; ++b) {
+        // 8 packed words -> the two planes, 2 elements per v_perm_b32
+        const uint32_t* xu = reinterpret_cast<const uint32_t*>(xp);
+        uint32_t wv[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) wv[i] = xu[pb[i] + off[b]];
+        u32x4 ph, pl;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          ph[i] = __builtin_amdgcn_perm(wv[2 * i + 1], wv[2 * i], 0x05040100u);  // lo halves: the hi plane
+          pl[i] = __builtin_amdgcn_perm(wv[2 * i + 1], wv[2 * i], 0x07060302u);  // hi halves: the lo plane
+        }
+        const sdb::bf16x8 bh = __builtin_bit_cast(sdb::bf16x8, ph), bl = __builtin_bit_cast(sdb::bf16x8, pl);
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          acc[i][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh, acc[i][b], 0, 0, 0);
+          acc[i][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl, acc[i][b], 0, 0, 0);
+          acc[i][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh, acc[i][b], 0, 0, 0);
+        }
+      }
+    }
+  }
+};
+
+// WS (wave split): for narrow j ranges (the 4-channel first stage: J + 1 = 101 -> 7 blocks) every wave covers all j
+// blocks over every 8th k step, and the 8 waves' tiles are summed through LDS at the end.
+// PL: dy is the max-pool backward's input (pooled resolution + argmax, sd_pool_rms_bwd_compact), expanded while it is
+// fetched — the full-resolution conv gradient (3/4 zeros) is never written to or read from HBM.
+template <class M, int TM, int NBW, bool WS>
+SD_DEV void wgrad_direct_body(const DirectW& d) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l16 = lane & 15, q = lane >> 4;
   const int P = d.R * d.W;
-  float* dyl = lds;                 // [P][SA]
-  float* xp = lds + P * d.SA;       // [PH][PW][CP]; channel Ci holds 1.0 (bias column), Ci+1 holds 0.0
+  M m(d, lds, tid);
   // per-lane column decode of this wave's j blocks (j == J -> the ones channel, j > J -> the zero channel)
   int off[NBW];
 #pragma unroll
@@ -895,28 +1109,12 @@ __global__ __launch_bounds__(512) void conv_wgrad_direct(DirectW d) {
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int b = 0; b < NBW; ++b) acc[i][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int rows_per_img = d.H / d.R, cq = d.Ci / 4, nA = P * d.Co / 4, nP = d.PH * d.PW * cq;
-  f32x4 ra[WD_VA], rp[WD_VP];
-  uint32_t aa[PL ? WD_VA : 1];
+  const int rows_per_img = d.H / d.R, cq = d.Ci / 4, nP = d.PH * d.PW * cq;
+  f32x4 rp[WD_VP];
   // global -> registers for row block rb (all loads issued together)
   auto fetch = [&](int rb) {
     const int n = rb / rows_per_img, y0 = (rb - n * rows_per_img) * d.R;
-    const float* dsrc = d.dy + ((long)n * d.H + y0) * d.W * d.Co;
-#pragma unroll
-    for (int v = 0; v < WD_VA; ++v) {
-      const int i = tid + 512 * v;
-      if constexpr (PL) {  // item i = (pooled pixel of the block, 4-channel group): raw gradient + argmax bytes
-        ra[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-        aa[v] = 0xffffffffu;
-        if (i < nA / 4) {
-          const long pp = (((long)n * (d.H >> 1) + (y0 >> 1)) * (d.W >> 1)) * d.Co + 4 * i;
-          ra[v] = *reinterpret_cast<const f32x4*>(d.dy + pp);
-          aa[v] = *reinterpret_cast<const uint32_t*>(d.amax + pp);
-        }
-      } else {
-        ra[v] = i < nA ? *reinterpret_cast<const f32x4*>(dsrc + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
+    m.fetch_dy(n, y0);
 #pragma unroll
     for (int v = 0; v < WD_VP; ++v) {
       const int i = tid + 512 * v;
@@ -932,41 +1130,17 @@ __global__ __launch_bounds__(512) void conv_wgrad_direct(DirectW d) {
     }
   };
   auto stage = [&]() {
-#pragma unroll
-    for (int v = 0; v < WD_VA; ++v) {
-      const int i = tid + 512 * v;
-      if constexpr (PL) {  // route the pooled gradient to its argmax position of the 2x2 window, zeros elsewhere
-        if (i < nA / 4) {
-          const int e = 4 * i, pl = e / d.Co, c = e - pl * d.Co;
-          const int hw = d.W >> 1, pr = pl / hw, pc = pl - pr * hw;
-#pragma unroll
-          for (int qd = 0; qd < 4; ++qd) {
-            const int p = (2 * pr + (qd >> 1)) * d.W + 2 * pc + (qd & 1);
-            f32x4 val;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) val[k] = ((aa[v] >> (8 * k)) & 0xffu) == (uint32_t)qd ? ra[v][k] : 0.f;
-            *reinterpret_cast<f32x4*>(dyl + p * d.SA + c) = val;
-          }
-        }
-      } else if (i < nA) {
-        const int e = 4 * i, p = e / d.Co, c = e - p * d.Co;
-        *reinterpret_cast<f32x4*>(dyl + p * d.SA + c) = ra[v];
-      }
-    }
+    m.stage_dy();
 #pragma unroll
     for (int v = 0; v < WD_VP; ++v) {
       const int i = tid + 512 * v;
       if (i < nP) {
         const int pix = i / cq, c = 4 * (i - pix * cq);
-        *reinterpret_cast<f32x4*>(xp + pix * d.CP + c) = rp[v];
+        m.stage_patch(pix, c, rp[v]);
       }
     }
   };
-  // the constant channels never change: write them once
-  for (int pix = tid; pix < d.PH * d.PW; pix += 512) {
-    xp[pix * d.CP + d.Ci] = 1.f;
-    xp[pix * d.CP + d.Ci + 1] = 0.f;
-  }
+  m.init();
   int rb = blockIdx.y;
   if (rb < d.blocks) fetch(rb);
   for (; rb < d.blocks; rb += gridDim.y) {
@@ -974,24 +1148,11 @@ __global__ __launch_bounds__(512) void conv_wgrad_direct(DirectW d) {
     stage();
     __syncthreads();
     if (rb + (int)gridDim.y < d.blocks) fetch(rb + gridDim.y);  // next block's loads overlap this block's MFMAs
-    for (int s = WS ? wave : 0; s < P / 4; s += WS ? NW_D : 1) {
-      const int p = 4 * s + q, py = p >> d.lw, px = p & (d.W - 1);
-      float a[TM];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) a[i] = dyl[p * d.SA + 16 * i + l16];
-      const float* xb = xp + (py * d.PW + px) * d.CP;
-      float bv[NBW];
-#pragma unroll
-      for (int b = 0; b < NBW; ++b) bv[b] = xb[off[b]];
-#pragma unroll
-      for (int b = 0; b < NBW; ++b)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) acc[i][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], bv[b], acc[i][b], 0, 0, 0);
-    }
+    m.template contract<NBW, WS>(acc, off, P, wave, l16, q);
   }
   // partial slab blockIdx.y: ws[split][co][J+1]
   float* out = d.ws + (long)blockIdx.y * d.Co * (d.J + 1);
-  if (WS) {  // sum the 8 waves' tiles through LDS (the staging area is free now), one 16x16 tile at a time
+  if constexpr (WS) {  // sum the 8 waves' tiles through LDS (the staging area is free now), one 16x16 tile at a time
 #pragma unroll
     for (int b = 0; b < NBW; ++b)
 #pragma unroll
@@ -1024,6 +1185,15 @@ __global__ __launch_bounds__(512) void conv_wgrad_direct(DirectW d) {
         }
     }
   }
+}
+
+template <int TM, int NBW, bool WS, bool PL = false>
+__global__ __launch_bounds__(512) void conv_wgrad_direct(DirectW d) {
+  wgrad_direct_body<WdF32<TM, PL>, TM, NBW, WS>(d);
+}
+template <int TM, int NBW, bool WS = false, bool PL = false>
+__global__ __launch_bounds__(512) void conv_wgrad3_direct(DirectW d) {
+  wgrad_direct_body<WdBf16x3<TM, PL>, TM, NBW, WS>(d);
 }
 
 // ---------------------------------------------------------------- split-bf16 backward (gemm3_core.h)
@@ -1238,229 +1408,6 @@ __global__ __launch_bounds__(256) void slab_reduce(const float* __restrict__ ws,
         const int tap = j / cx, c = j - tap * cx;
         if (c < acc.ci_w) acc.dw[(co * (J / cx) + tap) * acc.ci_w + c] += r;
       }
-    }
-  }
-}
-
-// ---------------------------------------------------------------- direct split-bf16 bwd-weight
-// conv_wgrad_direct's structure (one block of R image rows per step: the input patch with its halo staged in LDS
-// once, every (co, j) product of the block taken from LDS, partial slabs per blockIdx.y) on v_mfma_f32_16x16x32_bf16.
-// k = pixels, 32 per MFMA step: lane group q supplies pixels 4i + q (i = 0..7) of the step, so the 4 lane groups read
-// neighbouring pixels of the patch (CP floats apart: conflict-free) and each lane's 8 B-values are 8 ds_read_b32 at
-// precomputed pixel offsets + its column's tap offset, split to (hi, lo) in registers. dy of the block is staged
-// transposed and pre-split, [co][pos] per plane with pos = 8 (p % 4) + (p / 4) % 8 inside each 32-pixel step, so a
-// lane's 8 A-values (the same pixels) are one ds_read_b128 per plane. Wave w owns NBW 16-column blocks of j and all
-// TM 16-row blocks of co (rows >= Co read zero rows).
-struct DirectW3 {
-  const float* x;
-  const float* dy;      // (Nb, H, W, Co) conv-output gradient, or (PL) the pooled-resolution gradient
-  const uint8_t* amax;  // PL: the 2x2 max-pool argmax per pooled element
-  float* ws;
-  int Nb, H, W, Ci, Co, kh, kw, pad, R, lw;
-  int J, PW, PH, CP, PS, blocks;
-};
-
-// The input patch is staged PRE-SPLIT, each element as one 32-bit word (bf16 hi in the low half, bf16 lo in the high
-// half: the same split2 values), so the inner loop forms a lane's 8 B-values of each plane with 4 v_perm_b32. (The
-// first form staged f32 and re-split 8 floats per use, and every patch element feeds kh * kw taps x the column
-// blocks: bit-identical products, the split VALU moved from the k loop to the stage.)
-SD_DEV uint32_t pack_split(float v) {  // (bf16 hi | bf16 lo << 16), hi + lo = v up to 2^-17 |v| (split2's values)
-  const f32x4 x = {v, 0.f, 0.f, 0.f};
-  sdb::bf16x4 hi, lo;
-  sdb::split2(x, hi, lo);
-  return (uint32_t)__builtin_bit_cast(uint16_t, hi[0]) | ((uint32_t)__builtin_bit_cast(uint16_t, lo[0]) << 16);
-}
-// WS (wave split, as conv_wgrad_direct): for few column blocks (the 4-channel first stage: J + 1 = 101 -> 7 blocks)
-// every wave covers all of them over every 8th 32-pixel step, and the 8 waves' tiles are summed through LDS at the end.
-// PL: dy is the max-pool backward's pooled-resolution gradient + argmax (sd_pool_rms_bwd_compact), routed to its
-// window position while fetched (conv_wgrad_direct's PL): the first stage's bwd-weight without the full-resolution
-// conv gradient, on split-bf16.
-template <int TM, int NBW, bool WS = false, bool PL = false>
-__global__ __launch_bounds__(512) void conv_wgrad3_direct(DirectW3 d) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l16 = lane & 15, q = lane >> 4;
-  const int P = d.R * d.W;
-  float* xp = lds;  // [PH][PW][CP]; channel Ci holds 1.0 (bias column), Ci+1 holds 0.0
-  __bf16* dyh = reinterpret_cast<__bf16*>(lds + d.PH * d.PW * d.CP);  // [TM*16][PS]
-  __bf16* dyl = dyh + TM * 16 * d.PS;
-  for (int e = tid; e < TM * 16 * d.PS; e += 512) {  // rows >= Co stay zero; rows < Co are overwritten per block
-    dyh[e] = (__bf16)0.f;
-    dyl[e] = (__bf16)0.f;
-  }
-  int off[NBW];
-#pragma unroll
-  for (int b = 0; b < NBW; ++b) {
-    const int j = 16 * (WS ? b : (blockIdx.x * NW_D + wave) * NBW + b) + l16;
-    if (j < d.J) {
-      const int t = j / d.Ci, ci = j - t * d.Ci, ky = t / d.kw, kx = t - ky * d.kw;
-      off[b] = (ky * d.PW + kx) * d.CP + ci;
-    } else {
-      off[b] = d.Ci + (j == d.J ? 0 : 1);
-    }
-  }
-  f32x4 acc[TM][NBW];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int b = 0; b < NBW; ++b) acc[i][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int rows_per_img = d.H / d.R, cq = d.Ci / 4, nP = d.PH * d.PW * cq;
-  const int c4 = d.Co / 4, nD = c4 * (P / 4);  // 4x4 blocks: 8 pixel groups per 32-pixel step
-  // this thread's dy block: 4 channels x 4 pixels (pixels c + 4 (4 ih + t) of 32-pixel step sb, t = 0..3)
-  const int dq4 = tid % c4, drest = tid / c4;
-  const int dc = drest % 4, dih = (drest / 4) % 2, dsb = drest / 8;
-  f32x4 rd[4], rp[WD_VP];
-  uint32_t aw[PL ? 4 : 1];  // PL: the 4 channels' argmax bytes of each pixel's pooled element
-  int qd[PL ? 4 : 1];       // PL: the pixel's position in its 2x2 window
-  auto fetch = [&](int rb) {
-    const int n = rb / rows_per_img, y0 = (rb - n * rows_per_img) * d.R;
-    [[maybe_unused]] const float* dsrc = d.dy + ((long)n * d.H + y0) * d.W * d.Co;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int px = 32 * dsb + dc + 4 * (4 * dih + t);
-      if constexpr (PL) {  // the pooled element of pixel px (row y0 + px / W), loaded whole; masked in stage()
-        const int yy = y0 + (px >> d.lw), xx = px & (d.W - 1);
-        const long pp = (((long)n * (d.H >> 1) + (yy >> 1)) * (d.W >> 1) + (xx >> 1)) * d.Co + 4 * dq4;
-        const bool ok = tid < nD;
-        rd[t] = ok ? *reinterpret_cast<const f32x4*>(d.dy + pp) : f32x4{0.f, 0.f, 0.f, 0.f};
-        aw[t] = ok ? *reinterpret_cast<const uint32_t*>(d.amax + pp) : 0xffffffffu;
-        qd[t] = (yy & 1) * 2 + (xx & 1);
-      } else {
-        rd[t] = tid < nD ? *reinterpret_cast<const f32x4*>(dsrc + (long)px * d.Co + 4 * dq4)
-                         : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-#pragma unroll
-    for (int v = 0; v < WD_VP; ++v) {
-      const int i = tid + 512 * v;
-      f32x4 x = {0.f, 0.f, 0.f, 0.f};
-      if (i < nP) {
-        const int pix = i / cq, c = 4 * (i - pix * cq);
-        const int py = pix / d.PW, px = pix - py * d.PW;
-        const int iy = y0 - d.pad + py, ix = px - d.pad;
-        if (iy >= 0 && iy < d.H && ix >= 0 && ix < d.W)
-          x = *reinterpret_cast<const f32x4*>(d.x + (((long)n * d.H + iy) * d.W + ix) * d.Ci + c);
-      }
-      rp[v] = x;
-    }
-  };
-  auto stage = [&]() {
-    if (tid < nD) {
-      const int pos = 32 * dsb + 8 * dc + 4 * dih;
-      if constexpr (PL) {  // route the pooled gradient to its argmax position of the 2x2 window, zeros elsewhere
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (((aw[t] >> (8 * k)) & 0xffu) != (uint32_t)qd[t]) rd[t][k] = 0.f;
-      }
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const f32x4 t = {rd[0][jj], rd[1][jj], rd[2][jj], rd[3][jj]};
-        sdb::bf16x4 hi, lo;
-        sdb::split2(t, hi, lo);
-        const int o = (4 * dq4 + jj) * d.PS + pos;
-        *reinterpret_cast<sdb::bf16x4*>(dyh + o) = hi;
-        *reinterpret_cast<sdb::bf16x4*>(dyl + o) = lo;
-      }
-    }
-#pragma unroll
-    for (int v = 0; v < WD_VP; ++v) {
-      const int i = tid + 512 * v;
-      if (i < nP) {
-        const int pix = i / cq, c = 4 * (i - pix * cq);
-        sdb::bf16x4 hi, lo;
-        sdb::split2(rp[v], hi, lo);
-        const uint64_t h = __builtin_bit_cast(uint64_t, hi), l = __builtin_bit_cast(uint64_t, lo);
-        typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-        u32x4_ w;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = (uint32_t)((h >> (16 * k)) & 0xffffu) | ((uint32_t)((l >> (16 * k)) & 0xffffu) << 16);
-        *reinterpret_cast<u32x4_*>(xp + pix * d.CP + c) = w;
-      }
-    }
-  };
-  for (int pix = tid; pix < d.PH * d.PW; pix += 512) {
-    reinterpret_cast<uint32_t*>(xp)[pix * d.CP + d.Ci] = pack_split(1.f);
-    reinterpret_cast<uint32_t*>(xp)[pix * d.CP + d.Ci + 1] = 0u;
-  }
-  int rb = blockIdx.y;
-  if (rb < d.blocks) fetch(rb);
-  for (; rb < d.blocks; rb += gridDim.y) {
-    __syncthreads();  // previous block's LDS reads are done
-    stage();
-    __syncthreads();
-    if (rb + (int)gridDim.y < d.blocks) fetch(rb + gridDim.y);  // next block's loads overlap this block's MFMAs
-    for (int s = WS ? wave : 0; s < P / 32; s += WS ? NW_D : 1) {
-      sdb::bf16x8 ah[TM], al[TM];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int o = (16 * i + l16) * d.PS + 32 * s + 8 * q;
-        ah[i] = *reinterpret_cast<const sdb::bf16x8*>(dyh + o);
-        al[i] = *reinterpret_cast<const sdb::bf16x8*>(dyl + o);
-      }
-      int pb[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int p = 32 * s + 4 * i + q, py = p >> d.lw, px = p & (d.W - 1);
-        pb[i] = (py * d.PW + px) * d.CP;
-      }
-#pragma unroll
-      for (int b = 0; b < NBW; ++b) {
-        // 8 packed words -> the two planes, 2 elements per v_perm_b32
-        const uint32_t* xu = reinterpret_cast<const uint32_t*>(xp);
-        uint32_t wv[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wv[i] = xu[pb[i] + off[b]];
-        typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-        u32x4_ ph, pl;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          ph[i] = __builtin_amdgcn_perm(wv[2 * i + 1], wv[2 * i], 0x05040100u);  // lo halves: the hi plane
-          pl[i] = __builtin_amdgcn_perm(wv[2 * i + 1], wv[2 * i], 0x07060302u);  // hi halves: the lo plane
-        }
-        const sdb::bf16x8 bh = __builtin_bit_cast(sdb::bf16x8, ph), bl = __builtin_bit_cast(sdb::bf16x8, pl);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          acc[i][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh, acc[i][b], 0, 0, 0);
-          acc[i][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl, acc[i][b], 0, 0, 0);
-          acc[i][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh, acc[i][b], 0, 0, 0);
-        }
-      }
-    }
-  }
-  float* out = d.ws + (long)blockIdx.y * d.Co * (d.J + 1);
-  if constexpr (WS) {  // sum the 8 waves' tiles through LDS (the staging area is free now), one 16x16 tile at a time
-#pragma unroll
-    for (int b = 0; b < NBW; ++b)
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) lds[(wave * 4 + r) * 64 + lane] = acc[i][b][r];
-        __syncthreads();
-        if (tid < 256) {
-          const int r = tid >> 6, ln = tid & 63;
-          float v = 0.f;
-#pragma unroll
-          for (int w = 0; w < NW_D; ++w) v += lds[(w * 4 + r) * 64 + ln];
-          const int j = 16 * b + (ln & 15), co = 16 * i + 4 * (ln >> 4) + r;
-          if (j <= d.J && co < d.Co) out[(long)co * (d.J + 1) + j] = v;
-        }
-      }
-    return;
-  }
-#pragma unroll
-  for (int b = 0; b < NBW; ++b) {
-    const int j = 16 * ((blockIdx.x * NW_D + wave) * NBW + b) + l16;
-    if (j <= d.J) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int co = 16 * i + 4 * q + r;
-          if (co < d.Co) out[(long)co * (d.J + 1) + j] = acc[i][b][r];
-        }
     }
   }
 }
@@ -1742,20 +1689,40 @@ void wgrad_tile(GemmArgs& g, Geom& G, int J, bool va, bool vb, hipStream_t s) {
 
 int vpt_for(int C, int T) { int v = (C + T - 1) / T; return v <= 1 ? 1 : v <= 2 ? 2 : v <= 4 ? 4 : 8; }
 
-}  // namespace
-
-// out (Nb, Hg, Wg, Co) = conv_same(in (Nb, Hs, Ws, Ci) [upsampled x2 if ups], w (Co, kh, kw, Ci)) + bias
-// host side of the direct bwd-weight: row-block size, j blocking, split count (shared with the workspace query)
+// ---------------------------------------------------------------- direct bwd-weight: host plans and launcher
+// row-block size, j blocking, split count (shared with the workspace queries) and the staging geometry
 struct DirectPlan {
   int R, nbw, gx, gy, slabs;
   bool ws;
   size_t lds;
+  int PH, PW, CP, DS;
 };
 int patch_stride(int Ci) {  // >= Ci + 2 (ones / zero channels), % 4 == 0, 16 or 48 (mod 64) for wide Ci
   if (Ci < 16) return (Ci + 2 + 3) / 4 * 4;
   int c = (Ci + 2 + 15) / 16 * 16;
   while (c % 64 != 16 && c % 64 != 48) c += 16;
   return c;
+}
+int col_blocks(int kh, int kw, int Ci) { return (kh * kw * Ci + 1 + 15) / 16; }  // 16-column blocks of [dW | db]
+
+// The tail of the four plans, from R, ws, nbw and gx: the staged patch and dy block (x3: the split-bf16 layout), their
+// LDS and the grid. False where the staging does not fit.
+bool plan_tail(DirectPlan& pl, bool x3, int Nb, int H, int W, int Ci, int Co, int kh, int kw) {
+  const int P = pl.R * W;
+  pl.PH = pl.R + kh - 1, pl.PW = W + kw - 1, pl.CP = patch_stride(Ci);
+  pl.DS = x3 ? P + 8 : Co % 32 == 0 ? Co + 16 : Co;
+  const size_t dy_bytes = x3 ? (size_t)((Co + 15) / 16) * 16 * pl.DS * 2 * 2 : (size_t)P * pl.DS * 4;
+  pl.lds = (size_t)pl.PH * pl.PW * pl.CP * 4 + dy_bytes;
+  if (pl.lds > 160 * 1024 || pl.PH * pl.PW * (Ci / 4) > WD_VP * 512) return false;
+  // the wave-split kernel sums its NW_D waves' 16 x 16 tiles through the first NW_D * 4 * 64 floats of LDS at the end:
+  // a block that stages less (a 4 x 4 image of 4 channels: 2176 bytes) still gets that much
+  if (pl.ws && pl.lds < (size_t)NW_D * 4 * 64 * sizeof(float)) pl.lds = (size_t)NW_D * 4 * 64 * sizeof(float);
+  const int blocks = Nb * (H / pl.R);
+  pl.gy = 256 / pl.gx;
+  if (pl.gy > blocks) pl.gy = blocks;
+  if (pl.gy < 1) pl.gy = 1;
+  pl.slabs = pl.gy;
+  return true;
 }
 
 // pixels per staged row block of the max-pool-fused f32 direct bwd-weight (encoder first stage): more pixels per
@@ -1769,73 +1736,123 @@ bool direct_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, int ups, 
   if (ups != 0 || Co % 16 || Co > 64 || Ci % 4 || ilog2_exact(W) < 0) return false;
   const int pix = pool ? pool_pix : 128;
   pl.R = W >= pix ? 1 : (pix / W < H ? pix / W : H);
-  if (H % pl.R || (pl.R * W) % 4) return false;
-  const int SA = Co % 32 == 0 ? Co + 16 : Co, CP = patch_stride(Ci);
-  const int PH = pl.R + kh - 1, PW = W + kw - 1;
-  pl.lds = ((size_t)pl.R * W * SA + (size_t)PH * PW * CP) * 4;
-  if (pl.lds > 160 * 1024) return false;
-  if (pl.R * W * Co / (pool ? 16 : 4) > WD_VA * 512 || PH * PW * (Ci / 4) > WD_VP * 512) return false;
-  const int J = kh * kw * Ci, JB = (J + 1 + 15) / 16;
+  if (H % pl.R || (pl.R * W) % 4 || pl.R * W * Co / (pool ? 16 : 4) > WD_VA * 512) return false;
+  const int JB = col_blocks(kh, kw, Ci);
   pl.ws = JB <= 7;  // few column blocks: split the pixels over the waves instead
   pl.nbw = pl.ws ? 7 : JB <= 16 ? 2 : JB <= 32 ? 4 : JB <= 56 ? 7 : (Co <= 48 ? 10 : 7);
   pl.gx = pl.ws ? 1 : (JB + NW_D * pl.nbw - 1) / (NW_D * pl.nbw);
-  // the wave-split kernel sums its NW_D waves' 16 x 16 tiles through the first NW_D * 4 * 64 floats of LDS at the end:
-  // a block that stages less (a 4 x 4 image of 4 channels: 2176 bytes) still gets that much
-  if (pl.ws && pl.lds < (size_t)NW_D * 4 * 64 * sizeof(float)) pl.lds = (size_t)NW_D * 4 * 64 * sizeof(float);
-  const int blocks = Nb * (H / pl.R);
-  pl.gy = 256 / pl.gx;
-  if (pl.gy > blocks) pl.gy = blocks;
-  if (pl.gy < 1) pl.gy = 1;
-  pl.slabs = pl.gy;
+  return plan_tail(pl, false, Nb, H, W, Ci, Co, kh, kw);
+}
+
+// the pooled plan at the largest block (<= WGRAD_POOL_PIX) whose staging fits
+bool pool_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, DirectPlan& pl) {
+  if (H % 2 || W % 2) return false;
+  for (int pix = WGRAD_POOL_PIX; pix >= 128; pix /= 2)
+    if (direct_plan(Nb, H, W, Ci, Co, kh, kw, 0, pl, pix) && pl.ws && pl.nbw == 7 && pl.R % 2 == 0) return true;
+  return false;
+}
+
+// (Ci < 16 is refused: the encoder's 4-channel first stage has its own plan, pool3_plan, or the f32 direct kernel)
+bool direct3_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, int ups, DirectPlan& pl) {
+  if (ups != 0 || Co % 4 || Co > 64 || Ci % 4 || Ci < 16 || W < 8 || ilog2_exact(W) < 0 || W > 128) return false;
+  pl.R = 128 / W < H ? 128 / W : H;
+  const int P = pl.R * W, JB = col_blocks(kh, kw, Ci);
+  if (H % pl.R || P % 32 || (Co / 4) * (P / 4) > 512) return false;
+  pl.ws = false;
+  // column blocks per wave: the accumulators (TM * NBW * 4 VGPRs) bound it
+  const int nmax = Co <= 48 ? 7 : 4;
+  pl.gx = (JB + NW_D * nmax - 1) / (NW_D * nmax);
+  const int need = (JB + NW_D * pl.gx - 1) / (NW_D * pl.gx);
+  pl.nbw = need <= 2 ? 2 : need <= 4 ? 4 : need <= 5 ? 5 : 7;
+  return plan_tail(pl, true, Nb, H, W, Ci, Co, kh, kw);
+}
+
+// the first stage's plan for conv_wgrad3_direct<TM, 7, WS, PL>: dy at pooled resolution (R even), every wave over
+// all <= 7 column blocks (J + 1 <= 112), 32-pixel steps dealt to the 8 waves: R rows of W pixels with 8 steps per
+// block (P = 256), one 4-channel x 4-pixel dy item per thread ((Co / 4) (P / 4) <= 512)
+bool pool3_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, DirectPlan& pl) {
+  if (Co % 4 || Co > 64 || Ci % 4 || W < 8 || ilog2_exact(W) < 0 || W > 256 || H % 2) return false;
+  if (col_blocks(kh, kw, Ci) > 7) return false;
+  pl.R = 256 / W;
+  if (pl.R < 2 || pl.R % 2 || H % pl.R || (Co / 4) * (pl.R * W / 4) > 512) return false;
+  pl.ws = true;
+  pl.nbw = 7;
+  pl.gx = 1;
+  if (!plan_tail(pl, true, Nb, H, W, Ci, Co, kh, kw)) return false;
+  if (Nb < 1) pl.gy = pl.slabs = 0;  // this plan's query answers 0 slabs for no images (the others answer 1)
   return true;
 }
 
-int wgrad_direct(const float* in, const float* dout, float* dw_db, float* ws, long ws_floats, int Nb, int H, int W,
-                 int Ci, int Co, int kh, int kw, int pad, int J, int lw, const DirectPlan& pl, hipStream_t s,
-                 const uint8_t* amax, sd_wgrad_acc acc) {
-  DirectW d;
-  d.x = in; d.dy = dout; d.amax = amax; d.Nb = Nb; d.H = H; d.W = W; d.Ci = Ci; d.Co = Co; d.kh = kh; d.kw = kw; d.pad = pad;
-  d.lw = lw; d.J = J; d.R = pl.R;
-  d.PW = W + kw - 1; d.PH = d.R + kh - 1;
-  d.SA = Co % 32 == 0 ? Co + 16 : Co;
-  d.CP = patch_stride(Ci);
-  d.blocks = Nb * (H / d.R);
-  const size_t lds = pl.lds;
-  const int nbw = pl.nbw, gx = pl.gx, gy = pl.gy;
-  if (!ws || ws_floats < (long)pl.slabs * Co * (J + 1)) return SD_EARG;
-  d.ws = ws;
-  const dim3 grid(gx, gy);
-  const int TM = Co / 16;
-#define SD_WD_PL(TM_, NB_, WS_, PL_)                                                                       \
-  if (TM == TM_ && nbw == NB_ && pl.ws == WS_ && (amax != nullptr) == PL_) {                               \
-    static bool raised = false;                                                                            \
-    if (!raised && lds > 65536) {                                                                          \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_direct<TM_, NB_, WS_, PL_>),        \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)       \
-        return SD_EARG;                                                                                    \
-      raised = true;                                                                                       \
-    }                                                                                                      \
-    conv_wgrad_direct<TM_, NB_, WS_, PL_><<<grid, 512, lds, s>>>(d);                                       \
-    launched = true;                                                                                       \
-  }
-#define SD_WD(TM_, NB_, WS_) SD_WD_PL(TM_, NB_, WS_, false)
-  bool launched = false;
-  SD_WD(1, 7, true) SD_WD(2, 7, true) SD_WD(3, 7, true) SD_WD(4, 7, true)
-  SD_WD_PL(1, 7, true, true) SD_WD_PL(2, 7, true, true) SD_WD_PL(3, 7, true, true) SD_WD_PL(4, 7, true, true)
-  SD_WD(1, 2, false) SD_WD(1, 4, false) SD_WD(1, 7, false) SD_WD(1, 10, false)
-  SD_WD(2, 2, false) SD_WD(2, 4, false) SD_WD(2, 7, false) SD_WD(2, 10, false)
-  SD_WD(3, 2, false) SD_WD(3, 4, false) SD_WD(3, 7, false) SD_WD(3, 10, false)
-  SD_WD(4, 2, false) SD_WD(4, 4, false) SD_WD(4, 7, false)
-#undef SD_WD
-#undef SD_WD_PL
-  if (!launched) return SD_ESHAPE;
+// Dynamic LDS above the 64 KiB default has to be granted per kernel: done once, at the kernel's first such launch.
+template <auto KERNEL>
+bool raise_lds(int bytes) {
+  static bool raised = false;
+  if (!raised && hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     bytes) != hipSuccess)
+    return false;
+  return raised = true;
+}
+
+// The rungs <TM, NBW, WS, PL> the plans can reach (tests/test_conv_parity_cpu.py enumerates them): 23 of the f32
+// kernel, 16 of the split-bf16 one (x3). direct3_plan asks for at most 4 column blocks per wave at TM 4 and pool3_plan
+// admits Co <= 32, so <4,5>, <4,7>, <3,7,WS,PL> and <4,7,WS,PL> of the split-bf16 kernel do not exist.
+constexpr bool wd_rung(bool x3, int tm, int nbw, bool ws, bool pl) {
+  if (!x3) return ws ? nbw == 7 : !pl && (nbw == 2 || nbw == 4 || nbw == 7 || (nbw == 10 && tm <= 3));
+  if (ws || pl) return ws && pl && nbw == 7 && tm <= 2;
+  return nbw == 2 || nbw == 4 || (tm <= 3 && (nbw == 5 || nbw == 7));
+}
+template <bool X3, int TM, int NBW, bool WS, bool PL>
+constexpr auto wd_kernel() {
+  if constexpr (X3) return &conv_wgrad3_direct<TM, NBW, WS, PL>;
+  else return &conv_wgrad_direct<TM, NBW, WS, PL>;
+}
+template <int... Vs, class F>
+void with_int(int v, F&& f) {  // f(std::integral_constant<int, V>) for the V of the list that equals v
+  ((v == Vs ? f(std::integral_constant<int, Vs>{}) : void()), ...);
+}
+
+// One launch of the plan's rung on the f32 or the split-bf16 (X3) kernel, then the fixed-order sum of its slabs.
+// amax set: the pooled-gradient form (PL).
+template <bool X3>
+int wgrad_direct(const float* in, const float* dout, const uint8_t* amax, float* dw_db, float* ws, long ws_floats,
+                 int Nb, int H, int W, int Ci, int Co, int kh, int kw, int pad, const DirectPlan& pl, hipStream_t s,
+                 sd_wgrad_acc acc) {
+  const int J = kh * kw * Ci;
+  const long n = (long)Co * (J + 1);
+  if (!ws || ws_floats < pl.slabs * n) return SD_EARG;
+  const DirectW d{in, dout, amax, ws, Nb, H, W, Ci, Co, kh, kw, pad, pl.R, ilog2_exact(W),
+                  J, pl.PW, pl.PH, pl.CP, pl.DS, Nb * (H / pl.R)};
+  int rc = SD_ESHAPE;  // no such rung
+  with_int<1, 2, 3, 4>((Co + 15) / 16, [&](auto TM) {
+    with_int<2, 4, 5, 7, 10>(pl.nbw, [&](auto NBW) {
+      with_bools(
+          [&](auto WS, auto PL) {
+            constexpr int tm = decltype(TM)::value, nbw = decltype(NBW)::value;
+            constexpr bool wsplit = decltype(WS)::value, pooled = decltype(PL)::value;
+            if constexpr (wd_rung(X3, tm, nbw, wsplit, pooled)) {
+              constexpr auto kernel = wd_kernel<X3, tm, nbw, wsplit, pooled>();
+              rc = pl.lds > 65536 && !raise_lds<kernel>(160 * 1024) ? SD_EARG : SD_OK;
+              if (rc == SD_OK) kernel<<<dim3(pl.gx, pl.gy), 512, pl.lds, s>>>(d);
+            }
+          },
+          pl.ws, amax != nullptr);
+    });
+  });
+  if (rc != SD_OK) return rc;
   SD_LAUNCH_CHECK();
-  const long total = (long)Co * (J + 1);  // fixed-order sum of the row-block slabs (4 waves x unrolled loads)
-  slab_reduce<<<(int)((total + 63) / 64), 256, 0, s>>>(ws, pl.slabs, total, dw_db, acc, J, Ci);
+  slab_reduce<<<(int)((n + 63) / 64), 256, 0, s>>>(ws, pl.slabs, n, dw_db, acc, J, Ci);  // 4 waves x unrolled loads
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
 
+// the optional parameter-gradient target of the bwd-weight entries; false for an inconsistent one
+bool wgrad_acc_arg(const sd_wgrad_acc* acc_p, int Ci, sd_wgrad_acc& acc) {
+  acc = acc_p ? *acc_p : sd_wgrad_acc{nullptr, nullptr, 0};
+  return !acc.dw || (acc.db && acc.ci_w >= 1 && acc.ci_w <= Ci);
+}
+}  // namespace
+
+// out (Nb, Hg, Wg, Co) = conv_same(in (Nb, Hs, Ws, Ci) [upsampled x2 if ups], w (Co, kh, kw, Ci)) + bias
 extern "C" int sd_conv2d_fwd(const float* in, const float* w, const float* bias, float* out, int Nb, int Hs, int Ws,
                              int Ci, int Co, int kh, int kw, int pad, int ups, sd_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
@@ -1939,8 +1956,8 @@ extern "C" int sd_conv2d_wgrad(const float* in, const float* dout, float* dw_db,
                                const sd_wgrad_acc* acc_p, sd_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (Nb <= 0) return SD_OK;
-  const sd_wgrad_acc acc = acc_p ? *acc_p : sd_wgrad_acc{nullptr, nullptr, 0};
-  if (acc.dw && (!acc.db || acc.ci_w < 1 || acc.ci_w > Ci || !dw_db)) return SD_EARG;
+  sd_wgrad_acc acc;
+  if (!wgrad_acc_arg(acc_p, Ci, acc) || (acc.dw && !dw_db)) return SD_EARG;
   Geom G{in, Nb, Hs, Ws, Ci, Hs << ups, Ws << ups, kh, kw, pad, ups};
   const int J = kh * kw * Ci;
   GemmArgs g{};
@@ -1956,8 +1973,8 @@ extern "C" int sd_conv2d_wgrad(const float* in, const float* dout, float* dw_db,
   const bool vb = (Ci % 4 == 0) && aligned16(in);
   DirectPlan pl;
   if (va && vb && direct_plan(Nb, Hs, Ws, Ci, Co, kh, kw, ups, pl))
-    return wgrad_direct(in, dout, dw_db, workspace, ws_floats, Nb, Hs, Ws, Ci, Co, kh, kw, pad, J, ilog2_exact(G.Wg),
-                        pl, s, nullptr, acc);
+    return wgrad_direct<false>(in, dout, nullptr, dw_db, workspace, ws_floats, Nb, Hs, Ws, Ci, Co, kh, kw, pad, pl,
+                               s, acc);
   if (Co <= 32) wgrad_tile<32, 128, 32, 32>(g, G, J, va, vb, s);
   else wgrad_tile<64, 64, 32, 32>(g, G, J, va, vb, s);
   SD_LAUNCH_CHECK();
@@ -1980,13 +1997,6 @@ extern "C" int sd_conv2d_wgrad_slabs(int Nb, int Hs, int Ws, int Ci, int Co, int
   return ksplit < 1 ? 1 : ksplit;
 }
 
-// the pooled plan at the largest block (<= WGRAD_POOL_PIX) whose staging fits
-static bool pool_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, DirectPlan& pl) {
-  if (H % 2 || W % 2) return false;
-  for (int pix = WGRAD_POOL_PIX; pix >= 128; pix /= 2)
-    if (direct_plan(Nb, H, W, Ci, Co, kh, kw, 0, pl, pix) && pl.ws && pl.nbw == 7 && pl.R % 2 == 0) return true;
-  return false;
-}
 // bwd-weight of a pooled stage straight from the max-pool backward's pooled-resolution gradient + argmax
 // (sd_pool_rms_bwd_compact): the direct f32 kernel expands it while staging. SD_ESHAPE outside the direct plan.
 extern "C" int sd_conv2d_wgrad_pool_slabs(int Nb, int H, int W, int Ci, int Co, int kh, int kw) {
@@ -1998,16 +2008,16 @@ extern "C" int sd_conv2d_wgrad_pool(const float* in, const float* dpool, const u
                                     float* workspace, long ws_floats, int Nb, int H, int W, int Ci, int Co, int kh,
                                     int kw, int pad, const sd_wgrad_acc* acc_p, sd_stream stream_) {
   if (Nb <= 0) return SD_OK;
-  const sd_wgrad_acc acc = acc_p ? *acc_p : sd_wgrad_acc{nullptr, nullptr, 0};
-  if (acc.dw && (!acc.db || acc.ci_w < 1 || acc.ci_w > Ci)) return SD_EARG;
+  sd_wgrad_acc acc;
+  if (!wgrad_acc_arg(acc_p, Ci, acc)) return SD_EARG;
   DirectPlan pl;
   if (!pool_plan(Nb, H, W, Ci, Co, kh, kw, pl))
     return SD_ESHAPE;
   // amax is read as uint32 words (4 pooled pixels' argmax bytes per load)
   if (!aligned16(dpool) || !aligned16(in) || Co % 4 || Ci % 4 || !amax || reinterpret_cast<uintptr_t>(amax) % 4)
     return SD_EARG;
-  return wgrad_direct(in, dpool, dw_db, workspace, ws_floats, Nb, H, W, Ci, Co, kh, kw, pad, kh * kw * Ci,
-                      ilog2_exact(W), pl, (hipStream_t)stream_, amax, acc);
+  return wgrad_direct<false>(in, dpool, amax, dw_db, workspace, ws_floats, Nb, H, W, Ci, Co, kh, kw, pad, pl,
+                             (hipStream_t)stream_, acc);
 }
 
 extern "C" int sd_conv_flip_weight(const float* w, float* wf, int Co, int kh, int kw, int Ci, sd_stream s) {
@@ -2169,101 +2179,6 @@ extern "C" int sd_pool_rms_bwd_compact_film(const float* pooled, const uint8_t* 
                                       dbeta, film_partial, Nb, H, W, C, nchw_flat, accumulate_dw, stream_);
 }
 
-// ---------------------------------------------------------------- split-bf16 backward entry points
-namespace {
-// (Ci < 16 is refused: the encoder's 4-channel first stage has its own plan, pool3_plan, or the f32 direct kernel)
-bool direct3_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, int ups, DirectPlan& pl) {
-  if (ups != 0 || Co % 4 || Co > 64 || Ci % 4 || Ci < 16 || W < 8 || ilog2_exact(W) < 0 || W > 128) return false;
-  pl.R = 128 / W < H ? 128 / W : H;
-  const int P = pl.R * W;
-  if (H % pl.R || P % 32) return false;
-  const int TM = (Co + 15) / 16, CP = patch_stride(Ci);
-  const int PH = pl.R + kh - 1, PW = W + kw - 1;
-  pl.lds = (size_t)PH * PW * CP * 4 + (size_t)TM * 16 * (P + 8) * 2 * 2;
-  if (pl.lds > 160 * 1024 || PH * PW * (Ci / 4) > WD_VP * 512 || (Co / 4) * (P / 4) > 512) return false;
-  const int J = kh * kw * Ci, JB = (J + 1 + 15) / 16;
-  pl.ws = false;
-  // column blocks per wave: the accumulators (TM * NBW * 4 VGPRs) bound it
-  const int nmax = TM <= 3 ? 7 : 4;
-  pl.gx = (JB + NW_D * nmax - 1) / (NW_D * nmax);
-  const int need = (JB + NW_D * pl.gx - 1) / (NW_D * pl.gx);
-  pl.nbw = need <= 2 ? 2 : need <= 4 ? 4 : need <= 5 ? 5 : 7;
-  const int blocks = Nb * (H / pl.R);
-  pl.gy = 256 / pl.gx;
-  if (pl.gy > blocks) pl.gy = blocks;
-  if (pl.gy < 1) pl.gy = 1;
-  pl.slabs = pl.gy;
-  return true;
-}
-
-// the first stage's plan for conv_wgrad3_direct<TM, 7, WS, PL>: dy at pooled resolution (R even), every wave over
-// all <= 7 column blocks (J + 1 <= 112), 32-pixel steps dealt to the 8 waves: R rows of W pixels with 8 steps per
-// block (P = 256), one 4-channel x 4-pixel dy item per thread ((Co / 4) (P / 4) <= 512)
-bool pool3_plan(int Nb, int H, int W, int Ci, int Co, int kh, int kw, DirectPlan& pl) {
-  if (Co % 4 || Co > 64 || Ci % 4 || W < 8 || ilog2_exact(W) < 0 || W > 256 || H % 2) return false;
-  const int J = kh * kw * Ci, JB = (J + 1 + 15) / 16;
-  if (JB > 7) return false;
-  pl.R = 256 / W;
-  if (pl.R < 2 || pl.R % 2 || H % pl.R) return false;
-  const int P = pl.R * W, TM = (Co + 15) / 16, CP = patch_stride(Ci);
-  const int PH = pl.R + kh - 1, PW = W + kw - 1;
-  if ((Co / 4) * (P / 4) > 512 || PH * PW * (Ci / 4) > WD_VP * 512) return false;
-  pl.lds = (size_t)PH * PW * CP * 4 + (size_t)TM * 16 * (P + 8) * 2 * 2;
-  if (pl.lds > 160 * 1024) return false;
-  pl.ws = true;
-  pl.nbw = 7;
-  pl.gx = 1;
-  const int blocks = Nb * (H / pl.R);
-  pl.gy = blocks < 256 ? blocks : 256;
-  pl.slabs = pl.gy;
-  return true;
-}
-
-int wgrad3_direct(const float* in, const float* dout, float* dw_db, float* ws, long ws_floats, int Nb, int H, int W,
-                  int Ci, int Co, int kh, int kw, int pad, const DirectPlan& pl, hipStream_t s, sd_wgrad_acc acc,
-                  const uint8_t* amax = nullptr) {
-  DirectW3 d;
-  d.x = in; d.dy = dout; d.amax = amax; d.Nb = Nb; d.H = H; d.W = W; d.Ci = Ci; d.Co = Co; d.kh = kh; d.kw = kw;
-  d.pad = pad;
-  d.lw = ilog2_exact(W); d.J = kh * kw * Ci; d.R = pl.R;
-  d.PW = W + kw - 1; d.PH = d.R + kh - 1;
-  d.CP = patch_stride(Ci);
-  d.PS = d.R * W + 8;
-  d.blocks = Nb * (H / d.R);
-  if (!ws || ws_floats < (long)pl.slabs * Co * (d.J + 1)) return SD_EARG;
-  d.ws = ws;
-  const dim3 grid(pl.gx, pl.gy);
-  const int TM = (Co + 15) / 16;
-  bool launched = false;
-#define SD_WD3X(TM_, NB_, WS_, PL_)                                                                        \
-  if (TM == TM_ && pl.nbw == NB_ && pl.ws == WS_ && (amax != nullptr) == PL_) {                            \
-    static bool raised = false;                                                                            \
-    if (!raised && pl.lds > 65536) {                                                                       \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad3_direct<TM_, NB_, WS_, PL_>),       \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)       \
-        return SD_EARG;                                                                                    \
-      raised = true;                                                                                       \
-    }                                                                                                      \
-    conv_wgrad3_direct<TM_, NB_, WS_, PL_><<<grid, 512, pl.lds, s>>>(d);                                  \
-    launched = true;                                                                                       \
-  }
-#define SD_WD3(TM_, NB_) SD_WD3X(TM_, NB_, false, false)
-  SD_WD3(1, 2) SD_WD3(1, 4) SD_WD3(1, 5) SD_WD3(1, 7)
-  SD_WD3(2, 2) SD_WD3(2, 4) SD_WD3(2, 5) SD_WD3(2, 7)
-  SD_WD3(3, 2) SD_WD3(3, 4) SD_WD3(3, 5) SD_WD3(3, 7)
-  SD_WD3(4, 2) SD_WD3(4, 4) SD_WD3(4, 5) SD_WD3(4, 7)
-  SD_WD3X(1, 7, true, true) SD_WD3X(2, 7, true, true) SD_WD3X(3, 7, true, true) SD_WD3X(4, 7, true, true)
-#undef SD_WD3
-#undef SD_WD3X
-  if (!launched) return SD_ESHAPE;
-  SD_LAUNCH_CHECK();
-  const long n = (long)Co * (d.J + 1);
-  slab_reduce<<<(int)((n + 63) / 64), 256, 0, s>>>(ws, pl.slabs, n, dw_db, acc, d.J, Ci);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
-}
-}  // namespace
-
 extern "C" int sd_conv2d_dgrad_bf16x3(const float* dout, const float* wflip, float* din, int Nb, int Hs, int Ws,
                                       int Ci, int Co, int kh, int kw, int pad, sd_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
@@ -2313,13 +2228,7 @@ int fwd6r_launch_t(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp,
   constexpr int W = 1 << LW, R = MT * 128 / W;
   constexpr size_t lds = (size_t)3 * (R + KS - 1) * (W + KS - 1) * CI * 2 + (size_t)2 * 3 * BN * BROW * 2;
   static_assert(lds <= 160 * 1024, "LDS");
-  static bool raised = false;
-  if (!raised) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd6r_direct_pool<BN, CI, LW, KS, TPW, MT, BROW, NW>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return SD_EARG;
-    raised = true;
-  }
+  if (!raise_lds<&conv_fwd6r_direct_pool<BN, CI, LW, KS, TPW, MT, BROW, NW>>((int)lds)) return SD_EARG;
   const int nwg = (sd_cdiv(g.M / (MT * 128), TPW) + 7) / 8 * 8;  // a multiple of 8: XCD-contiguous
   conv_fwd6r_direct_pool<BN, CI, LW, KS, TPW, MT, BROW, NW><<<nwg, 512, lds, s>>>(g, G, lhw, wsp, nw, pooled, amax, y,
                                                                                   rstd, eps, nchw_flat);
@@ -2350,13 +2259,7 @@ int fwd6_launch(const GemmArgs& g, const Geom& G, int lhw, const __bf16* wsp, NW
 #undef SD_F6R
   }
   const size_t lds = (size_t)3 * (R + KS - 1) * (W + KS - 1) * (CI + 8) * 2;
-  static bool raised = false;
-  if (!raised && lds > 65536) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd6_direct_pool<BN, CI, LW, KS, NW>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return SD_EARG;
-    raised = true;
-  }
+  if (lds > 65536 && !raise_lds<&conv_fwd6_direct_pool<BN, CI, LW, KS, NW>>((int)lds)) return SD_EARG;
   conv_fwd6_direct_pool<BN, CI, LW, KS, NW><<<g.M / 128, 256, lds, s>>>(g, G, lhw, wsp, nw, pooled, amax, y, rstd, eps,
                                                                    nchw_flat);
   SD_LAUNCH_CHECK();
@@ -2420,13 +2323,7 @@ int dgrad_direct_launch(const float* dout, const __bf16* wsp, float* din, int Nb
   constexpr size_t lds = (size_t)2 * (R + KS - 1) * (W + KS - 1) * CIN * 2 + (size_t)2 * 2 * (16 * NT) * 40 * 2;
   static_assert(lds <= 160 * 1024, "LDS");
   if (H % R) return SD_ESHAPE;
-  static bool raised = false;
-  if (!raised) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dgrad3_direct<CIN, NT, LW, KS, NTHR>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return SD_EARG;
-    raised = true;
-  }
+  if (!raise_lds<&conv_dgrad3_direct<CIN, NT, LW, KS, NTHR>>((int)lds)) return SD_EARG;
   conv_dgrad3_direct<CIN, NT, LW, KS, NTHR><<<Nb * (H / R), NTHR, lds, s>>>(dout, wsp, din, Nb, H, pad);
   SD_LAUNCH_CHECK();
   return SD_OK;
@@ -2463,13 +2360,13 @@ extern "C" int sd_conv2d_wgrad_pool_bf16x3(const float* in, const float* dpool, 
                                            float* workspace, long ws_floats, int Nb, int H, int W, int Ci, int Co,
                                            int kh, int kw, int pad, const sd_wgrad_acc* acc_p, sd_stream stream_) {
   if (Nb <= 0) return SD_OK;
-  const sd_wgrad_acc acc = acc_p ? *acc_p : sd_wgrad_acc{nullptr, nullptr, 0};
-  if (acc.dw && (!acc.db || acc.ci_w < 1 || acc.ci_w > Ci)) return SD_EARG;
+  sd_wgrad_acc acc;
+  if (!wgrad_acc_arg(acc_p, Ci, acc)) return SD_EARG;
   DirectPlan pl;
   if (!pool3_plan(Nb, H, W, Ci, Co, kh, kw, pl)) return SD_ESHAPE;
   if (!aligned16(dpool) || !aligned16(in) || !amax || reinterpret_cast<uintptr_t>(amax) % 4) return SD_EARG;
-  return wgrad3_direct(in, dpool, dw_db, workspace, ws_floats, Nb, H, W, Ci, Co, kh, kw, pad, pl,
-                       (hipStream_t)stream_, acc, amax);
+  return wgrad_direct<true>(in, dpool, amax, dw_db, workspace, ws_floats, Nb, H, W, Ci, Co, kh, kw, pad, pl,
+                            (hipStream_t)stream_, acc);
 }
 
 extern "C" int sd_conv2d_wgrad_bf16x3(const float* in, const float* dout, float* dw_db, float* workspace,
@@ -2477,11 +2374,12 @@ extern "C" int sd_conv2d_wgrad_bf16x3(const float* in, const float* dout, float*
                                       const sd_wgrad_acc* acc_p, sd_stream stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (Nb <= 0) return SD_OK;
-  const sd_wgrad_acc acc = acc_p ? *acc_p : sd_wgrad_acc{nullptr, nullptr, 0};
-  if (acc.dw && (!acc.db || acc.ci_w < 1 || acc.ci_w > Ci)) return SD_EARG;
+  sd_wgrad_acc acc;
+  if (!wgrad_acc_arg(acc_p, Ci, acc)) return SD_EARG;
   DirectPlan pl;
   if (!direct3_plan(Nb, Hs, Ws, Ci, Co, kh, kw, 0, pl) || !aligned16(in) || !aligned16(dout)) return SD_ESHAPE;
-  return wgrad3_direct(in, dout, dw_db, workspace, ws_floats, Nb, Hs, Ws, Ci, Co, kh, kw, pad, pl, s, acc);
+  return wgrad_direct<true>(in, dout, nullptr, dw_db, workspace, ws_floats, Nb, Hs, Ws, Ci, Co, kh, kw, pad, pl,
+                            s, acc);
 }
 
 // ---------------------------------------------------------------- first-stage input gradient from the pooled gradient

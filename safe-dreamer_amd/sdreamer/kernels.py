@@ -602,6 +602,23 @@ def _wgrad_acc(acc):
     return a, ctypes.addressof(a)
 
 
+def _wgrad_call(name, ks, shape, acc, ptrs, tail, shaped=False):
+    """One bwd-weight launch: out (Co, J + 1) and a workspace of ks slabs (the direct kernels write a slab per
+    row-block group and reduce them: one slab needs its workspace too), then
+    name(*ptrs, out, workspace, floats, *tail, acc, stream). Returns out (None with acc), or False where `shaped`
+    (nat.call_shaped) and the entry refuses the shape."""
+    Co, J, dev = shape
+    out = torch.empty(Co, J + 1, dtype=torch.float32, device=dev)
+    ws = torch.empty(ks * Co * (J + 1), dtype=torch.float32, device=dev)
+    keep, ap = _wgrad_acc(acc)
+    call = nat.call_shaped if shaped else nat.call
+    taken = call(name, *ptrs, p(out), p(ws), ws.numel(), *tail, ap, stream())
+    del keep
+    if taken is False:
+        return False
+    return None if acc is not None else out
+
+
 def conv2d_wgrad(x, dout, kh, kw, ups=0, pad=None, fast=True, acc=None):
     """returns (Co, kh*kw*Ci + 1) = [dW | db]. fast: split-bf16 direct kernel (sd_conv2d_wgrad_bf16x3) where eligible
     (Ci >= 16; the 4-channel first layer keeps the f32 direct kernel). acc = (dw, db, ci_w): the result is added into
@@ -610,29 +627,22 @@ def conv2d_wgrad(x, dout, kh, kw, ups=0, pad=None, fast=True, acc=None):
     Co = dout.shape[-1]
     pad = (kh - 1) // 2 if pad is None else pad
     J = kh * kw * Ci
-    keep, ap = _wgrad_acc(acc)
+    shape, ptrs = (Co, J, x.device), (p(_c(x)), p(_c(dout)))
     if fast and FAST_GEMM:
         ks = nat.fns["sd_conv2d_wgrad_bf16x3_slabs"](Nb, H, W, Ci, Co, kh, kw, ups)
         if ks > 0:
-            out = torch.empty(Co, J + 1, dtype=torch.float32, device=x.device)
-            # the direct kernels write a slab per row-block group and reduce them: one slab needs its workspace too
-            ws = torch.empty(ks * Co * (J + 1), dtype=torch.float32, device=x.device)
-            if nat.call_shaped("sd_conv2d_wgrad_bf16x3", p(_c(x)), p(_c(dout)), p(out), p(ws), ws.numel(),
-                               Nb, H, W, Ci, Co, kh, kw, pad, ap, stream()):
-                return None if acc is not None else out
+            out = _wgrad_call("sd_conv2d_wgrad_bf16x3", ks, shape, acc, ptrs, (Nb, H, W, Ci, Co, kh, kw, pad),
+                              shaped=True)
+            if out is not False:
+                return out
     pixels = dout.numel() // Co
     ks = max(1, min(256, pixels // 4096))
     tiles = -(-Co // 64) * -(-(J + 1) // 64)
     ks = max(1, min(ks, max(1, 1024 // tiles)))
-    out = torch.empty(Co, J + 1, dtype=torch.float32, device=x.device)
     ks = nat.fns["sd_conv2d_wgrad_slabs"](Nb, H, W, Ci, Co, kh, kw, ups, ks)
     # (ks == 1 is one slab of the f32 direct kernel, which needs it, or the implicit GEMM unsplit, which does not: the
     # query does not tell them apart)
-    ws = torch.empty(ks * Co * (J + 1), dtype=torch.float32, device=x.device)
-    nat.call("sd_conv2d_wgrad", p(_c(x)), p(_c(dout)), p(out), p(ws), ws.numel(), ks,
-             Nb, H, W, Ci, Co, kh, kw, pad, ups, ap, stream())
-    del keep
-    return None if acc is not None else out
+    return _wgrad_call("sd_conv2d_wgrad", ks, shape, acc, ptrs, (ks, Nb, H, W, Ci, Co, kh, kw, pad, ups))
 
 
 def conv2d_wgrad_pool_slabs(x, Co, kh, kw):
@@ -656,27 +666,16 @@ def conv2d_wgrad_pool(x, dpool, amax, kh, kw, pad=None, acc=None):
     Nb, H, W, Ci = x.shape
     Co = dpool.shape[-1]
     pad = (kh - 1) // 2 if pad is None else pad
-    J = kh * kw * Ci
+    shape, ptrs = (Co, kh * kw * Ci, x.device), (p(_c(x)), p(_c(dpool)), p(_c(amax)))
+    tail = (Nb, H, W, Ci, Co, kh, kw, pad)
     if WGRAD1_X3 and FAST_GEMM:
         ks = nat.fns["sd_conv2d_wgrad_pool_bf16x3_slabs"](Nb, H, W, Ci, Co, kh, kw)
         if ks > 0:
-            out = torch.empty(Co, J + 1, dtype=torch.float32, device=x.device)
-            ws = torch.empty(ks * Co * (J + 1), dtype=torch.float32, device=x.device)
-            keep, ap = _wgrad_acc(acc)
-            nat.call("sd_conv2d_wgrad_pool_bf16x3", p(_c(x)), p(_c(dpool)), p(_c(amax)), p(out), p(ws), ws.numel(),
-                     Nb, H, W, Ci, Co, kh, kw, pad, ap, stream())
-            del keep
-            return None if acc is not None else out
+            return _wgrad_call("sd_conv2d_wgrad_pool_bf16x3", ks, shape, acc, ptrs, tail)
     ks = conv2d_wgrad_pool_slabs(x, Co, kh, kw)
     if ks <= 0:
         raise nat.NativeError("sd_conv2d_wgrad_pool: shape outside the direct kernel")
-    out = torch.empty(Co, J + 1, dtype=torch.float32, device=x.device)
-    ws = torch.empty(ks * Co * (J + 1), dtype=torch.float32, device=x.device)
-    keep, ap = _wgrad_acc(acc)
-    nat.call("sd_conv2d_wgrad_pool", p(_c(x)), p(_c(dpool)), p(_c(amax)), p(out), p(ws), ws.numel(), Nb, H, W, Ci, Co,
-             kh, kw, pad, ap, stream())
-    del keep
-    return None if acc is not None else out
+    return _wgrad_call("sd_conv2d_wgrad_pool", ks, shape, acc, ptrs, tail)
 
 
 def conv2d_dgrad_pool_takes(H, W, Co, Ci, kh, kw, pad=None):

@@ -338,6 +338,10 @@ STAGE_CASES = [
     S("ci8_k3_nodx", 8, 16, 16, 16, 3, 2, False, "conv_fwd16_pool<16>", POOL3.format(1), "-"),
     S("ci12_k3", 12, 16, 8, 8, 3, 2, True, "conv_fwd16_pool<16>", "conv_wgrad_direct<1,7,WS>",
       "conv_fwd_kernel<128,32,VA,VB>"),
+    # ---- the f32 pooled kernel at 1, 3 and 4 blocks of 16 output channels (the first stage has 2)
+    S("pl_f32_tm1", 4, 16, 4, 4, 3, 2, False, "conv_fwd16<16> + pool_rms", POOLF.format(1, 4), "-", x3=False),
+    S("pl_f32_tm3", 4, 48, 4, 4, 3, 3, False, "conv_fwd16<48> + pool_rms", POOLF.format(3, 4), "-", x3=False),
+    S("pl_f32_tm4", 4, 64, 4, 4, 3, 1, False, "conv_fwd16<64> + pool_rms", POOLF.format(4, 4), "-", x3=False),
     # ---- anchors: the BASELINE stages at Nb 1 (64 -> 64 at 8 x 8: 64 pixels, half a tile; Nb 3: a ragged second tile)
     S("a_32_48", 32, 48, 32, 32, 5, 1, True, "conv_fwd6r_direct_pool", "conv_wgrad3_direct<3,7>", "conv_dgrad3_direct"),
     S("a_48_64", 48, 64, 16, 16, 5, 1, True, "conv_fwd6r_direct_pool", "conv_wgrad3_direct<4,4> gx=3",
@@ -391,6 +395,20 @@ KERNEL_CASES = [
     KC("wg_k4_h12", "wgrad", 16, 32, 12, 8, 4, 1, "conv_wgrad_direct<2,4>", "conv_wgrad3_direct<2,4>"),  # R = 12 of 16
     # one image row per block
     KC("wg_w128_r1", "wgrad", 16, 32, 3, 128, 3, 1, "conv_wgrad_direct<2,2>", "conv_wgrad3_direct<2,2>"),
+    # the rest of the rungs the plans can reach (test_conv_parity_cpu enumerates them), at the smallest shape of each
+    KC("wg_tm1_nbw2", "wgrad", 16, 16, 8, 8, 3, 2, "conv_wgrad_direct<1,2>", "conv_wgrad3_direct<1,2>"),
+    KC("wg_tm1_nbw4", "wgrad", 32, 16, 8, 8, 3, 3, "conv_wgrad_direct<1,4>", "conv_wgrad3_direct<1,4>"),
+    KC("wg_tm1_nbw7", "wgrad", 32, 16, 8, 8, 5, 1, "conv_wgrad_direct<1,7>", "conv_wgrad3_direct<1,7>"),
+    KC("wg_tm2_nbw7", "wgrad", 24, 32, 8, 8, 5, 2, "conv_wgrad_direct<2,7>", "conv_wgrad3_direct<2,5>"),
+    KC("wg_tm2_nbw10", "wgrad", 64, 32, 8, 8, 5, 1, "conv_wgrad_direct<2,10> gx=2", "conv_wgrad3_direct<2,7> gx=2"),
+    KC("wg_tm3_nbw2", "wgrad", 16, 48, 8, 8, 3, 2, "conv_wgrad_direct<3,2>", "conv_wgrad3_direct<3,2>"),
+    KC("wg_tm3_nbw7", "wgrad", 32, 48, 8, 8, 5, 1, "conv_wgrad_direct<3,7>", "conv_wgrad3_direct<3,7>"),
+    KC("wg_tm4_nbw2", "wgrad", 16, 64, 8, 8, 3, 3, "conv_wgrad_direct<4,2>", "conv_wgrad3_direct<4,2>"),
+    KC("wg_tm4_nbw4", "wgrad", 32, 64, 8, 8, 3, 1, "conv_wgrad_direct<4,4>", "conv_wgrad3_direct<4,4>"),
+    KC("wg_ws_tm3", "wgrad", 4, 48, 4, 4, 3, 2, "conv_wgrad_direct<3,7,WS>"),
+    KC("wg_ws_tm4", "wgrad", 4, 64, 4, 4, 3, 3, "conv_wgrad_direct<4,7,WS>"),
+    # 260 row blocks over 256 workgroup rows: four workgroups take a second block (prefetched), the others do not
+    KC("wg_nb260", "wgrad", 16, 16, 8, 8, 3, 260, "conv_wgrad_direct<1,2>", "conv_wgrad3_direct<1,2>"),
     KC("wg_ups_co3", "wgrad", 16, 3, 4, 4, 5, 2, "conv_wgrad_kernel<32,128,VB>", ups=1),
     # the four VA / VB forms of the split-K tiles
     KC("wg_ci3", "wgrad", 3, 16, 6, 5, 5, 2, "conv_wgrad_kernel<32,128,VA>"),

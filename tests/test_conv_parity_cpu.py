@@ -229,6 +229,36 @@ def test_plans_agree_with_the_library_over_a_sweep():
             cm.check_plans(nat, Nb, H, W, Ci, Co, 5)
 
 
+def test_every_reachable_rung_of_the_direct_kernels_is_named_by_a_case():
+    """csrc/conv.hip instantiates conv_wgrad_direct / conv_wgrad3_direct<TM, NBW, WS, PL> only at the rungs its four
+    plans can reach (WdF32Host::rung, WdBf16x3Host::rung: 23 + 16). The restated plans, enumerated over a grid of
+    shapes, reach exactly those, and every one of them is the arm of some case, so the float64 tests launch it."""
+    reached = {name: set() for name in ("direct", "direct3", "pool", "pool3")}
+    sizes = ((1, 3, 64), (2, 4, 6, 8, 12, 16, 32, 64, 128), [2 ** i for i in range(1, 9)], range(4, 129, 4),
+             range(4, 65, 4), (1, 2, 3, 4, 5, 7))
+    for Nb, H, W, Ci, Co, k in itertools.product(*sizes):
+        plans = dict(direct=cm.direct_plan(Nb, H, W, Ci, Co, k, k), direct3=cm.direct3_plan(Nb, H, W, Ci, Co, k, k),
+                     pool=cm.pool_plan(Nb, H, W, Ci, Co, k, k), pool3=cm.pool3_plan(Nb, H, W, Ci, Co, k, k))
+        for name, pl in plans.items():
+            if pl:
+                reached[name].add((pl["tm"], pl["nbw"], pl["ws"]))
+    tms = (1, 2, 3, 4)
+    want = dict(direct={(tm, nbw, False) for tm in tms for nbw in (2, 4, 7)} | {(tm, 10, False) for tm in (1, 2, 3)}
+                | {(tm, 7, True) for tm in tms},
+                direct3={(tm, nbw, False) for tm in (1, 2, 3) for nbw in (2, 4, 5, 7)} | {(4, 2, False), (4, 4, False)},
+                pool={(tm, 7, True) for tm in tms},
+                pool3={(1, 7, True), (2, 7, True)})
+    assert reached == want
+    assert sum(len(s) for s in want.values()) == 23 + 16
+    labels = {c.wgrad.split(" ")[0] for c in cm.STAGE_CASES + cm.UP_CASES}
+    labels |= {a.split(" ")[0] for c in cm.KERNEL_CASES if c.op == "wgrad" for a in (c.arm, c.fast) if a}
+    for name, rungs in want.items():
+        kernel = "conv_wgrad3_direct" if name.endswith("3") else "conv_wgrad_direct"
+        for tm, nbw, ws in sorted(rungs):
+            arm = f"{kernel}<{tm},{nbw}{',WS' if ws else ''}{',PL' if name.startswith('pool') else ''}>"
+            assert arm in labels, f"no case reaches {arm}"
+
+
 def test_wave_split_plan_reserves_its_reduction_area():
     """A wave-split plan sums its 8 waves' 16 x 16 tiles through 8 KiB of LDS after the last row block: its request
     covers that where the staged block is smaller (a 4 x 4 image of 4 channels stages 2176 bytes)."""

@@ -1,7 +1,7 @@
-"""Bit-identity check between two builds of libsdhip.so (A/B aid): computes the split-bf16 conv bwd-weight /
-bwd-data, the fused imagination of the bench agent (random init, seed 0) and the parameters after two eager updates
-of that agent on the bench's synthetic buffer, on fixed inputs, with the library SDHIP_LIB points at, and saves them to
-argv[1]; `python tools/lib_bitcheck.py cmp a.npz b.npz` reports whether every array is bit-identical."""
+"""Bit-identity check between two builds of libsdhip.so (A/B aid): computes the split-bf16 and f32 conv bwd-weight, the
+pooled-gradient bwd-weight on both, the split-bf16 bwd-data, the fused imagination of the bench agent (random init,
+seed 0) and the parameters after two eager updates of that agent on the bench's synthetic buffer, on fixed inputs,
+with the library SDHIP_LIB points at, and saves them to argv[1]; `python tools/lib_bitcheck.py cmp a.npz b.npz` reports whether every array is bit-identical."""
 import os
 import sys
 
@@ -21,7 +21,17 @@ def run(out):
         dy = torch.randn(nb, hw, hw, co, generator=g).cuda()
         w = (torch.randn(co, 5, 5, ci, generator=g) / (ci * 25) ** 0.5).cuda()
         res[f"dw_{ci}_{co}"] = K.conv2d_wgrad(x, dy, 5, 5, fast=True).cpu().numpy()
+        res[f"dw_f32_{ci}_{co}"] = K.conv2d_wgrad(x, dy, 5, 5, fast=False).cpu().numpy()
         res[f"dx_{ci}_{co}"] = K.conv2d_dgrad(dy, w, fast=True).cpu().numpy()
+    # the first stage's pooled-gradient bwd-weight (the loop's last shape: 4 -> 32 at 64 x 64, 8 images) on the
+    # split-bf16 and on the f32 kernel
+    dpool = torch.randn(nb, hw // 2, hw // 2, co, generator=g).cuda()
+    amax = torch.randint(0, 4, dpool.shape, generator=g).to(torch.uint8).cuda()
+    x3_default = K.WGRAD1_X3
+    for x3 in (True, False):
+        K.WGRAD1_X3 = x3
+        res[f"dw_pool_x3_{int(x3)}"] = K.conv2d_wgrad_pool(x, dpool, amax, 5, 5).cpu().numpy()
+    K.WGRAD1_X3 = x3_default
     import bench
     from sdreamer.config import load_config
     from sdreamer.dreamer import Dreamer
