@@ -865,6 +865,12 @@ struct DirectW {
 
 constexpr int WD_VA = 4, WD_VP = 6;  // max float4 per thread of a staged dy block (f32 path) / input patch
 
+// column j < J = (ky, kx, ci): its tap's pixel shift + its channel, in elements of a [PH][PW][CP] patch image
+SD_DEV int wd_tap_off(const DirectW& d, int j) {
+  const int t = j / d.Ci, ci = j - t * d.Ci, ky = t / d.kw, kx = t - ky * d.kw;
+  return (ky * d.PW + kx) * d.CP + ci;
+}
+
 // The f32 path. MFMA 16x16x4: lane (l16, q) supplies dy[p = 4s+q][co = l16] and x-patch[p = 4s+q][j = l16].
 // LDS row strides are padded to 16 (mod 64) floats so the 4 lane groups hit distinct banks.
 template <int TM, bool PL>
@@ -882,6 +888,11 @@ struct WdF32 {
       xp[pix * d.CP + d.Ci] = 1.f;
       xp[pix * d.CP + d.Ci + 1] = 0.f;
     }
+  }
+  // this lane's column of the block starting at j0 (j == J -> the ones channel, j > J -> the zero channel)
+  SD_DEV int col_off(int j0, int l16) const {
+    const int j = j0 + l16;
+    return j < d.J ? wd_tap_off(d, j) : d.Ci + (j == d.J ? 0 : 1);
   }
   SD_DEV void fetch_dy(int n, int y0) {
     const float* dsrc = d.dy + ((long)n * d.H + y0) * d.W * d.Co;
@@ -944,29 +955,32 @@ struct WdF32 {
   }
 };
 
-SD_DEV uint32_t pack_split(float v) {  // (bf16 hi | bf16 lo << 16), hi + lo = v up to 2^-17 |v| (split2's values)
-  const f32x4 x = {v, 0.f, 0.f, 0.f};
-  sdb::bf16x4 hi, lo;
-  sdb::split2(x, hi, lo);
-  return (uint32_t)__builtin_bit_cast(uint16_t, hi[0]) | ((uint32_t)__builtin_bit_cast(uint16_t, lo[0]) << 16);
-}
-
 // The split-bf16 path, on v_mfma_f32_16x16x32_bf16 (~1e-5 relative, three products per step).
-// k = pixels, 32 per MFMA step: lane group q supplies pixels 4i + q (i = 0..7) of the step, so the 4 lane groups read
-// neighbouring pixels of the patch (CP floats apart: conflict-free) and each lane's 8 B-values are 8 ds_read_b32 at
-// precomputed pixel offsets + its column's tap offset. dy of the block is staged transposed and pre-split,
-// [co][pos] per plane with pos = 8 (p % 4) + (p / 4) % 8 inside each 32-pixel step, so a lane's 8 A-values (the same
-// pixels) are one ds_read_b128 per plane (rows >= Co read zero rows).
-// The input patch is staged PRE-SPLIT, each element as one 32-bit word (bf16 hi in the low half, bf16 lo in the high
-// half: the same split2 values), so the inner loop forms a lane's 8 B-values of each plane with 4 v_perm_b32. (The
-// first form staged f32 and re-split 8 floats per use, and every patch element feeds kh * kw taps x the column
-// blocks: bit-identical products, the split VALU moved from the k loop to the stage.)
+// k = pixels, 32 per MFMA step: lane group q supplies pixels 4i + q (i = 0..7) of the step. dy of the block is staged
+// transposed and pre-split, [co][pos] per plane with pos = 8 (p % 4) + (p / 4) % 8 inside each 32-pixel step, so a
+// lane's 8 A-values are one ds_read_b128 per plane (rows >= Co read zero rows).
+// The input patch is staged PRE-SPLIT as two bf16 planes, hi and lo (split2's values), each [PH][PW][CP] with the
+// channels contiguous, and the B operand comes from transposed reads: per column block and plane two
+// ds_read_b64_tr_b16, each a 4-pixel x 16-column block per 16-lane group, delivered column-major. In group q, lane
+// 4 r + c (r, c = 0..3) supplies the address of pixel 4 r + q (second read: 4 (r + 4) + q) of the step, shifted by
+// the tap of column quad 16 b + 4 c, at that quad's first channel; lane l16 receives column 16 b + l16 of the 4
+// pixels, so the two reads are the lane's k = 0..3 and 4..7: the operands of the word-gather form this replaces (8
+// ds_read_b32 and 4 v_perm_b32 per column block), in the same slots, bit for bit. A quad never straddles a tap
+// (Ci % 4 == 0 and a block starts at a multiple of 16), though a block may span several (Ci = 4: four; Ci = 24).
+// The constant channels are the quad [1, 0, 0, 0] at Ci .. Ci + 3 (column J is the bias column). Quads past J read
+// that quad as well: B column n reaches only column n of the tile, and no column past J is stored.
+// What the transposed read asks for: every lane's address 8-byte aligned (CP, Ci and every channel offset are
+// multiples of 4 elements, the plane bases multiples of 8 bytes), and EXEC all ones (512 threads, a k loop whose
+// bounds are scalar, no lane-dependent branch around the reads: every lane reads an in-bounds quad).
+// Banks ((a / 4) % 64 per 32-lane half = two neighbouring pixels x 4 pixels x 4 quads): 2-way at CP = 16 or 48
+// (mod 64) elements, the floor of any pixel stride for this k -> pixel assignment.
 template <int TM, bool PL>
 struct WdBf16x3 {
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(3))) sdb::bf16x4 lds_bf16x4;
   const DirectW& d;
   const int tid;
-  float* const xp;    // [PH][PW][CP] packed words; channel Ci holds 1.0 (bias column), Ci+1 holds 0.0
+  __bf16* const xh;   // [PH][PW][CP], the hi plane; channels Ci .. Ci+3 hold [1, 0, 0, 0]
+  __bf16* const xl;   // the lo plane, behind it (the constant quad is [0, 0, 0, 0] here)
   __bf16* const dyh;  // [TM*16][DS]
   __bf16* const dyl;
   // this thread's dy block: 4 channels x 4 pixels (pixels c + 4 (4 ih + t) of 32-pixel step sb, t = 0..3)
@@ -975,8 +989,8 @@ struct WdBf16x3 {
   uint32_t aw[PL ? 4 : 1];  // PL: the 4 channels' argmax bytes of each pixel's pooled element
   int qd[PL ? 4 : 1];       // PL: the pixel's position in its 2x2 window
   SD_DEV WdBf16x3(const DirectW& d_, float* lds, int tid_)
-      : d(d_), tid(tid_), xp(lds), dyh(reinterpret_cast<__bf16*>(lds + d_.PH * d_.PW * d_.CP)),
-        dyl(dyh + TM * 16 * d_.DS) {
+      : d(d_), tid(tid_), xh(reinterpret_cast<__bf16*>(lds)), xl(xh + d_.PH * d_.PW * d_.CP),
+        dyh(reinterpret_cast<__bf16*>(lds + d_.PH * d_.PW * d_.CP)), dyl(dyh + TM * 16 * d_.DS) {
     for (int e = tid; e < TM * 16 * d.DS; e += 512) {  // rows >= Co stay zero; rows < Co are overwritten per block
       dyh[e] = (__bf16)0.f;
       dyl[e] = (__bf16)0.f;
@@ -987,10 +1001,17 @@ struct WdBf16x3 {
     nD = c4 * (d.R * d.W / 4);
     dq4 = tid % c4;
     dc = drest % 4, dih = (drest / 4) % 2, dsb = drest / 8;
+    sdb::bf16x4 one, zero;
+    sdb::split2(f32x4{1.f, 0.f, 0.f, 0.f}, one, zero);
     for (int pix = tid; pix < d.PH * d.PW; pix += 512) {
-      reinterpret_cast<uint32_t*>(xp)[pix * d.CP + d.Ci] = pack_split(1.f);
-      reinterpret_cast<uint32_t*>(xp)[pix * d.CP + d.Ci + 1] = 0u;
+      *reinterpret_cast<sdb::bf16x4*>(xh + pix * d.CP + d.Ci) = one;
+      *reinterpret_cast<sdb::bf16x4*>(xl + pix * d.CP + d.Ci) = zero;
     }
+  }
+  // byte offset, from a pixel of a plane, of the quad this lane addresses in the column block starting at column j0
+  SD_DEV int col_off(int j0, int l16) const {
+    const int j = j0 + 4 * (l16 & 3);
+    return 2 * (j < d.J ? wd_tap_off(d, j) : d.Ci);
   }
   SD_DEV void fetch_dy(int n, int y0) {
     [[maybe_unused]] const float* dsrc = d.dy + ((long)n * d.H + y0) * d.W * d.Co;
@@ -1034,15 +1055,20 @@ struct WdBf16x3 {
   SD_DEV void stage_patch(int pix, int c, const f32x4& v) {
     sdb::bf16x4 hi, lo;
     sdb::split2(v, hi, lo);
-    const uint64_t h = __builtin_bit_cast(uint64_t, hi), l = __builtin_bit_cast(uint64_t, lo);
-    u32x4 w;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) w[k] = (uint32_t)((h >> (16 * k)) & 0xffffu) | ((uint32_t)((l >> (16 * k)) & 0xffffu) << 16);
-    *reinterpret_cast<u32x4*>(xp + pix * d.CP + c) = w;
+    *reinterpret_cast<sdb::bf16x4*>(xh + pix * d.CP + c) = hi;
+    *reinterpret_cast<sdb::bf16x4*>(xl + pix * d.CP + c) = lo;
+  }
+  static SD_DEV sdb::bf16x8 tr_pair(uint32_t a0, uint32_t a1) {  // two transposed reads: a lane's k = 0..3 | 4..7
+    const sdb::bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(reinterpret_cast<lds_bf16x4*>(a0));
+    const sdb::bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(reinterpret_cast<lds_bf16x4*>(a1));
+    return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
   }
   template <int NBW, bool WS>
   SD_DEV void contract(f32x4 (&acc)[TM][NBW], const int (&off)[NBW], int P, int wave, int l16, int q) {
-    for (int s = WS ? wave : 0; s < P / 32; s += WS ? NW_D : 1) {
+    // LDS byte addresses (the low half of a shared pointer's flat address is its LDS offset)
+    const uint32_t xh0 = (uint32_t)reinterpret_cast<uintptr_t>(xh), plane = 2u * d.PH * d.PW * d.CP;
+    const int s0 = WS ? __builtin_amdgcn_readfirstlane(wave) : 0;  // a scalar loop: EXEC stays all ones
+    for (int s = s0; s < P / 32; s += WS ? NW_D : 1) {
       sdb::bf16x8 ah[TM], al[TM];
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
@@ -1050,26 +1076,16 @@ struct WdBf16x3 {
         ah[i] = *reinterpret_cast<const sdb::bf16x8*>(dyh + o);
         al[i] = *reinterpret_cast<const sdb::bf16x8*>(dyl + o);
       }
-      int pb[8];
+      uint32_t pa[2];  // the hi plane's address of this lane's pixel row of each read
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int p = 32 * s + 4 * i + q, py = p >> d.lw, px = p & (d.W - 1);
-        pb[i] = (py * d.PW + px) * d.CP;
+      for (int r = 0; r < 2; ++r) {
+        const int p = 32 * s + 4 * ((l16 >> 2) + 4 * r) + q, py = p >> d.lw, px = p & (d.W - 1);
+        pa[r] = xh0 + 2u * ((py * d.PW + px) * d.CP);
       }
 #pragma unroll
       for (int b = 0; b < NBW; ++b) {
-        // 8 packed words -> the two planes, 2 elements per v_perm_b32
-        const uint32_t* xu = reinterpret_cast<const uint32_t*>(xp);
-        uint32_t wv[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wv[i] = xu[pb[i] + off[b]];
-        u32x4 ph, pl;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          ph[i] = __builtin_amdgcn_perm(wv[2 * i + 1], wv[2 * i], 0x05040100u);  // lo halves: the hi plane
-          pl[i] = __builtin_amdgcn_perm(wv[2 * i + 1], wv[2 * i], 0x07060302u);  // hi halves: the lo plane
-        }
-        const sdb::bf16x8 bh = __builtin_bit_cast(sdb::bf16x8, ph), bl = __builtin_bit_cast(sdb::bf16x8, pl);
+        const sdb::bf16x8 bh = tr_pair(pa[0] + off[b], pa[1] + off[b]);
+        const sdb::bf16x8 bl = tr_pair(pa[0] + off[b] + plane, pa[1] + off[b] + plane);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           acc[i][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh, acc[i][b], 0, 0, 0);
@@ -1092,18 +1108,10 @@ SD_DEV void wgrad_direct_body(const DirectW& d) {
   const int l16 = lane & 15, q = lane >> 4;
   const int P = d.R * d.W;
   M m(d, lds, tid);
-  // per-lane column decode of this wave's j blocks (j == J -> the ones channel, j > J -> the zero channel)
+  // per-lane decode of this wave's j blocks: the f32 path's column, the split-bf16 path's column quad
   int off[NBW];
 #pragma unroll
-  for (int b = 0; b < NBW; ++b) {
-    const int j = 16 * (WS ? b : (blockIdx.x * NW_D + wave) * NBW + b) + l16;
-    if (j < d.J) {
-      const int t = j / d.Ci, ci = j - t * d.Ci, ky = t / d.kw, kx = t - ky * d.kw;
-      off[b] = (ky * d.PW + kx) * d.CP + ci;
-    } else {
-      off[b] = d.Ci + (j == d.J ? 0 : 1);
-    }
-  }
+  for (int b = 0; b < NBW; ++b) off[b] = m.col_off(16 * (WS ? b : (blockIdx.x * NW_D + wave) * NBW + b), l16);
   f32x4 acc[TM][NBW];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -1697,7 +1705,10 @@ struct DirectPlan {
   size_t lds;
   int PH, PW, CP, DS;
 };
-int patch_stride(int Ci) {  // >= Ci + 2 (ones / zero channels), % 4 == 0, 16 or 48 (mod 64) for wide Ci
+// >= Ci + 2 (the f32 path's ones / zero channels) and, Ci % 4 == 0, >= Ci + 4 (the split-bf16 path's constant quad),
+// % 4 == 0, 16 or 48 (mod 64) for wide Ci: the f32 path's word reads are conflict-free, the split-bf16 path's
+// transposed reads of its two bf16 planes (the same stride in elements, so half these bytes each) 2-way
+int patch_stride(int Ci) {
   if (Ci < 16) return (Ci + 2 + 3) / 4 * 4;
   int c = (Ci + 2 + 15) / 16 * 16;
   while (c % 64 != 16 && c % 64 != 48) c += 16;
