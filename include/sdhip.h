@@ -288,6 +288,23 @@ int sd_conv2d_dgrad_pool(const float* dpool, const uint8_t* amax, const float* w
  * Conv2dSamePad (networks.py:59-85). */
 int sd_conv2d_dgrad_direct(const float* dout, const void* wsplit, float* din, int Nb, int Hs, int Ws, int Ci, int Co,
                            int kh, int kw, int pad, sd_stream stream);
+/* The two split-bf16 backward contractions of a pooled ConvEncoder stage from (dpool, argmax) of
+ * sd_pool_rms_bwd_compact[_film] (dpool, amax: (Nb, H/2, W/2, C of the conv output)): the kernels of
+ * sd_conv2d_wgrad_bf16x3 / sd_conv2d_dgrad_direct expand the pooled gradient through the argmax while they stage it in
+ * LDS, so the full-resolution conv gradient (3/4 zeros) is neither written nor read. The same values reach the same LDS
+ * slots: each result equals the full-resolution entry's on expand(dpool, amax) bit for bit.
+ * wgrad: sd_conv2d_wgrad_bf16x3's plan (the same kernel rung, row blocks, grid and slab count) where H is even as
+ * well; _slabs: the workspace slabs, 0 outside it (then the entry returns SD_ESHAPE). Alignment: in and dpool 16 B,
+ * amax 4 B (read as uint32 words), else SD_EARG.
+ * dgrad: sd_conv2d_dgrad_direct's two shapes, Hs x Ws the full resolution, Ci = dpool's channels, Co = din's;
+ * _ok: 1 where the shape is taken, else 0 (then the entry returns SD_ESHAPE). */
+int sd_conv2d_wgrad_bf16x3_pooled_slabs(int Nb, int H, int W, int Ci, int Co, int kh, int kw);
+int sd_conv2d_wgrad_bf16x3_pooled(const float* in, const float* dpool, const uint8_t* amax, float* dw_db,
+                                  float* workspace, long ws_floats, int Nb, int H, int W, int Ci, int Co, int kh,
+                                  int kw, int pad, const sd_wgrad_acc* acc, sd_stream stream);
+int sd_conv2d_dgrad_direct_pooled_ok(int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad);
+int sd_conv2d_dgrad_direct_pooled(const float* dpool, const uint8_t* amax, const void* wsplit, float* din, int Nb,
+                                  int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad, sd_stream stream);
 /* sd_conv2d_fwd_pool on the fp32-accurate three-way split-bf16 path (csrc/conv.hip conv_fwd6_direct_pool, gemm6_core.h
  * "bf16x6": six bf16 MFMAs per product, <= 2^-26 |ab| dropped per product, fp32-level error): a direct convolution from
  * the tile's input patch staged once in LDS as three bf16 planes. wsplit3 = sd_conv_split3_weight(w, rows = Co,

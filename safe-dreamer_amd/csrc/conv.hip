@@ -935,6 +935,7 @@ struct WdF32 {
       }
     }
   }
+  SD_DEV void settle_dy() {}
   SD_DEV void stage_patch(int pix, int c, const f32x4& v) { *reinterpret_cast<f32x4*>(xp + pix * d.CP + c) = v; }
   template <int NBW, bool WS>
   SD_DEV void contract(f32x4 (&acc)[TM][NBW], const int (&off)[NBW], int P, int wave, int l16, int q) {
@@ -974,7 +975,7 @@ struct WdF32 {
 // bounds are scalar, no lane-dependent branch around the reads: every lane reads an in-bounds quad).
 // Banks ((a / 4) % 64 per 32-lane half = two neighbouring pixels x 4 pixels x 4 quads): 2-way at CP = 16 or 48
 // (mod 64) elements, the floor of any pixel stride for this k -> pixel assignment.
-template <int TM, bool PL>
+template <int TM, bool PL, bool WSK = false>  // WSK: a wave-split rung (only its pooled-gradient fetch differs)
 struct WdBf16x3 {
   typedef __attribute__((address_space(3))) sdb::bf16x4 lds_bf16x4;
   const DirectW& d;
@@ -987,7 +988,7 @@ struct WdBf16x3 {
   int nD, dq4, dc, dih, dsb;  // nD 4x4 blocks: 8 pixel groups per 32-pixel step
   f32x4 rd[4];
   uint32_t aw[PL ? 4 : 1];  // PL: the 4 channels' argmax bytes of each pixel's pooled element
-  int qd[PL ? 4 : 1];       // PL: the pixel's position in its 2x2 window
+  int dy0;                  // PL: the fetched block's first image row (its parity places a pixel in its 2x2 window)
   SD_DEV WdBf16x3(const DirectW& d_, float* lds, int tid_)
       : d(d_), tid(tid_), xh(reinterpret_cast<__bf16*>(lds)), xl(xh + d_.PH * d_.PW * d_.CP),
         dyh(reinterpret_cast<__bf16*>(lds + d_.PH * d_.PW * d_.CP)), dyl(dyh + TM * 16 * d_.DS) {
@@ -1015,32 +1016,58 @@ struct WdBf16x3 {
   }
   SD_DEV void fetch_dy(int n, int y0) {
     [[maybe_unused]] const float* dsrc = d.dy + ((long)n * d.H + y0) * d.W * d.Co;
+    // PL, not WS: the block's first pooled row is a workgroup-uniform base and a pixel's pooled element a 32-bit offset
+    // from it ((y0 + r) / 2 == y0 / 2 + r / 2 for every row r of the block: R is even, and y0 with it, or R is 1),
+    // recomputed per block (px made opaque) instead of hoisted: as 64-bit element indices from d.dy the offsets kept 14
+    // loop-invariant registers live across the MFMA loop, and the <3, 7> rung then reloaded a spilled pointer between
+    // the two groups of loads, a full wait for the first group before the second was issued (+ 8 % on that launch).
+    // The wave-split first-stage rungs have the registers and little MFMA work to hide the recomputation under (it
+    // cost them 185 -> 223 us at 1,024 images): they keep the hoisted 64-bit form.
+    [[maybe_unused]] const long pbase = (((long)n * (d.H >> 1) + (y0 >> 1)) * (d.W >> 1)) * d.Co;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const int px = 32 * dsb + dc + 4 * (4 * dih + t);
+      int px = 32 * dsb + dc + 4 * (4 * dih + t);
       if constexpr (PL) {  // the pooled element of pixel px (row y0 + px / W), loaded whole; masked in stage_dy()
-        const int yy = y0 + (px >> d.lw), xx = px & (d.W - 1);
-        const long pp = (((long)n * (d.H >> 1) + (yy >> 1)) * (d.W >> 1) + (xx >> 1)) * d.Co + 4 * dq4;
+        long pp;
+        if constexpr (WSK) {
+          const int yy = y0 + (px >> d.lw), xx = px & (d.W - 1);
+          pp = (((long)n * (d.H >> 1) + (yy >> 1)) * (d.W >> 1) + (xx >> 1)) * d.Co + 4 * dq4;
+        } else {
+          asm volatile("" : "+v"(px));
+          pp = pbase + ((((px >> d.lw) >> 1) * (d.W >> 1) + ((px & (d.W - 1)) >> 1)) * d.Co + 4 * dq4);
+        }
         const bool ok = tid < nD;
         rd[t] = ok ? *reinterpret_cast<const f32x4*>(d.dy + pp) : f32x4{0.f, 0.f, 0.f, 0.f};
         aw[t] = ok ? *reinterpret_cast<const uint32_t*>(d.amax + pp) : 0xffffffffu;
-        qd[t] = (yy & 1) * 2 + (xx & 1);
+        dy0 = y0;
       } else {
         rd[t] = tid < nD ? *reinterpret_cast<const f32x4*>(dsrc + (long)px * d.Co + 4 * dq4)
                          : f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
   }
+  // PL: route the pooled gradient to its argmax position of the 2x2 window, zeros elsewhere
+  SD_DEV void mask_dy() {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int px = 32 * dsb + dc + 4 * (4 * dih + t);  // the pixel's position in its 2x2 window: row, column parity
+      const uint32_t qd = (uint32_t)(((dy0 + (px >> d.lw)) & 1) * 2 + (px & 1));
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (((aw[t] >> (8 * k)) & 0xffu) != qd) rd[t][k] = 0.f;
+    }
+  }
+  // Called after a block's MFMAs (and after the first fetch): the pooled form masks the fetched block here, in
+  // registers, while other waves still run their MFMAs, instead of between the two barriers of stage_dy, where every
+  // wave waits (the 32 compares and selects per thread there cost the <3, 7> rung what the smaller fetch gained it).
+  // The wave-split rungs, a single MFMA step per wave and block, keep the mask in stage_dy.
+  SD_DEV void settle_dy() {
+    if constexpr (PL && !WSK) mask_dy();
+  }
   SD_DEV void stage_dy() {
     if (tid < nD) {
       const int pos = 32 * dsb + 8 * dc + 4 * dih;
-      if constexpr (PL) {  // route the pooled gradient to its argmax position of the 2x2 window, zeros elsewhere
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (((aw[t] >> (8 * k)) & 0xffu) != (uint32_t)qd[t]) rd[t][k] = 0.f;
-      }
+      if constexpr (PL && WSK) mask_dy();
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
         const f32x4 t = {rd[0][jj], rd[1][jj], rd[2][jj], rd[3][jj]};
@@ -1150,13 +1177,18 @@ SD_DEV void wgrad_direct_body(const DirectW& d) {
   };
   m.init();
   int rb = blockIdx.y;
-  if (rb < d.blocks) fetch(rb);
+  if (rb < d.blocks) {
+    fetch(rb);
+    m.settle_dy();
+  }
   for (; rb < d.blocks; rb += gridDim.y) {
     __syncthreads();  // previous block's LDS reads are done
     stage();
     __syncthreads();
-    if (rb + (int)gridDim.y < d.blocks) fetch(rb + gridDim.y);  // next block's loads overlap this block's MFMAs
+    const bool more = rb + (int)gridDim.y < d.blocks;
+    if (more) fetch(rb + gridDim.y);  // next block's loads overlap this block's MFMAs
     m.template contract<NBW, WS>(acc, off, P, wave, l16, q);
+    if (more) m.settle_dy();
   }
   // partial slab blockIdx.y: ws[split][co][J+1]
   float* out = d.ws + (long)blockIdx.y * d.Co * (d.J + 1);
@@ -1201,7 +1233,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_direct(DirectW d) {
 }
 template <int TM, int NBW, bool WS = false, bool PL = false>
 __global__ __launch_bounds__(512) void conv_wgrad3_direct(DirectW d) {
-  wgrad_direct_body<WdBf16x3<TM, PL>, TM, NBW, WS>(d);
+  wgrad_direct_body<WdBf16x3<TM, PL, WS>, TM, NBW, WS>(d);
 }
 
 // ---------------------------------------------------------------- split-bf16 backward (gemm3_core.h)
@@ -1255,8 +1287,16 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad3(GemmArgs g, Geom G, int lw
 // waves: 12 fragment reads per 24 MFMAs instead of 8 per 12. Same products in the same k order. The first form, 128-pixel
 // tiles of 32-pixel waves (MT = 2) with a padded pixel-major patch, two workgroups per CU, was retired: 183 -> 131 us
 // alone on the 64 -> 48 stage (profiles/r06dg3).
-template <int CIN, int NT, int LW, int KS, int NTHR>
+// PL: dout is the max-pool backward's pooled-resolution gradient (Nb, H / 2, W / 2, CIN) and amax the forward's argmax
+// bytes (sd_pool_rms_bwd_compact): the full-resolution dOut (3/4 zeros) exists only in the LDS patch. A thread's item
+// is one pooled element x 4 channels of the pooled rows / columns whose 2x2 windows touch the patch (any parity of the
+// patch's first row and column): one f32x4 + 4 argmax bytes loaded, one split, and each of the window's four positions
+// inside the patch written with the value where the channel's argmax names the position and zero elsewhere. The
+// windows tile the plane, so every patch slot is written exactly once (pooled indices outside the image write zeros)
+// with the bits the full-resolution form stages there: same products, same k order, the same dIn bit for bit.
+template <int CIN, int NT, int LW, int KS, int NTHR, bool PL = false>
 __global__ __launch_bounds__(NTHR, 2) void conv_dgrad3_direct(const float* __restrict__ dout,
+                                                               const uint8_t* __restrict__ amax,
                                                                const __bf16* __restrict__ wsp, float* __restrict__ din,
                                                                int Nb, int H, int pad) {
   constexpr int MT = 4, TP = 16 * MT * (NTHR / 64);
@@ -1270,7 +1310,44 @@ __global__ __launch_bounds__(NTHR, 2) void conv_dgrad3_direct(const float* __res
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, q = lane >> 4;
   const int rows_per_img = H / R, n = blockIdx.x / rows_per_img, y0 = (blockIdx.x % rows_per_img) * R;
   // stage the patch: every load first, then split + store
-  {
+  if constexpr (PL) {
+    constexpr int NPR = PH / 2 + 1, NPC = PW / 2 + 1, NIT = NPR * NPC * CIN4, NI = (NIT + NTHR - 1) / NTHR;
+    const int Hp = H >> 1, Wp = W >> 1;
+    const int iy0 = y0 - pad, ix0 = -pad;        // image row / column of patch pixel (0, 0)
+    const int pr0 = iy0 >> 1, pc0 = ix0 >> 1;    // first pooled row / column touching the patch (floor)
+    f32x4 v[NI];
+    uint32_t aw[NI];
+#pragma unroll
+    for (int e = 0; e < NI; ++e) {
+      const int i = tid + NTHR * e, c4 = i % CIN4, pp = i / CIN4, pr = pr0 + pp / NPC, pc = pc0 + pp % NPC;
+      const bool ok = i < NIT && pr >= 0 && pr < Hp && pc >= 0 && pc < Wp;
+      const long o = (((long)n * Hp + pr) * Wp + pc) * CIN + 4 * c4;
+      v[e] = ok ? *reinterpret_cast<const f32x4*>(dout + o) : f32x4{0.f, 0.f, 0.f, 0.f};
+      aw[e] = ok ? *reinterpret_cast<const uint32_t*>(amax + o) : 0u;
+    }
+#pragma unroll
+    for (int e = 0; e < NI; ++e) {
+      const int i = tid + NTHR * e;
+      if (i < NIT) {
+        const int c4 = i % CIN4, pp = i / CIN4, pr = pr0 + pp / NPC, pc = pc0 + pp % NPC;
+        sdb::bf16x4 hi, lo;
+        sdb::split2(v[e], hi, lo);
+        const uint64_t hb = __builtin_bit_cast(uint64_t, hi), lb = __builtin_bit_cast(uint64_t, lo);
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+          const int r = 2 * pr + (qd >> 1) - iy0, c = 2 * pc + (qd & 1) - ix0;
+          if ((unsigned)r < (unsigned)PH && (unsigned)c < (unsigned)PW) {
+            uint64_t m = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (((aw[e] >> (8 * k)) & 0xffu) == (uint32_t)qd) m |= 0xffffull << (16 * k);
+            *reinterpret_cast<uint64_t*>(patch + poff(r * PW + c, 4 * c4)) = hb & m;
+            *reinterpret_cast<uint64_t*>(patch + PLANE + poff(r * PW + c, 4 * c4)) = lb & m;
+          }
+        }
+      }
+    }
+  } else {
     f32x4 v[NE];
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
@@ -1805,11 +1882,13 @@ bool raise_lds(int bytes) {
 }
 
 // The rungs <TM, NBW, WS, PL> the plans can reach (tests/test_conv_parity_cpu.py enumerates them): 23 of the f32
-// kernel, 16 of the split-bf16 one (x3). direct3_plan asks for at most 4 column blocks per wave at TM 4 and pool3_plan
-// admits Co <= 32, so <4,5>, <4,7>, <3,7,WS,PL> and <4,7,WS,PL> of the split-bf16 kernel do not exist.
+// kernel, 30 of the split-bf16 one (x3): direct3_plan's 14 in both forms of dy (full resolution, and PL: the pooled
+// gradient + argmax of sd_conv2d_wgrad_bf16x3_pooled, the same plan) and pool3_plan's 2. direct3_plan asks for at most
+// 4 column blocks per wave at TM 4 and pool3_plan admits Co <= 32, so <4,5>, <4,7>, <3,7,WS,PL> and <4,7,WS,PL> of the
+// split-bf16 kernel do not exist.
 constexpr bool wd_rung(bool x3, int tm, int nbw, bool ws, bool pl) {
   if (!x3) return ws ? nbw == 7 : !pl && (nbw == 2 || nbw == 4 || nbw == 7 || (nbw == 10 && tm <= 3));
-  if (ws || pl) return ws && pl && nbw == 7 && tm <= 2;
+  if (ws) return pl && nbw == 7 && tm <= 2;
   return nbw == 2 || nbw == 4 || (tm <= 3 && (nbw == 5 || nbw == 7));
 }
 template <bool X3, int TM, int NBW, bool WS, bool PL>
@@ -2327,17 +2406,36 @@ extern "C" int sd_conv_split_weight(const float* w, void* wsplit, int rows, int 
 
 namespace {
 // R whole image rows per workgroup as NTHR / 64 waves of 64 pixels, channel-group-major patch
-template <int CIN, int NT, int LW, int R, int NTHR>
-int dgrad_direct_launch(const float* dout, const __bf16* wsp, float* din, int Nb, int H, int pad, hipStream_t s) {
+// amax set: dout is the pooled-resolution gradient (PL)
+template <int CIN, int NT, int LW, int R, int NTHR, bool PL>
+int dgrad_direct_launch(const float* dout, const uint8_t* amax, const __bf16* wsp, float* din, int Nb, int H, int pad,
+                        hipStream_t s) {
   constexpr int W = 1 << LW, KS = 5;
   static_assert(R * W == NTHR, "64-pixel waves");
   constexpr size_t lds = (size_t)2 * (R + KS - 1) * (W + KS - 1) * CIN * 2 + (size_t)2 * 2 * (16 * NT) * 40 * 2;
   static_assert(lds <= 160 * 1024, "LDS");
   if (H % R) return SD_ESHAPE;
-  if (!raise_lds<&conv_dgrad3_direct<CIN, NT, LW, KS, NTHR>>((int)lds)) return SD_EARG;
-  conv_dgrad3_direct<CIN, NT, LW, KS, NTHR><<<Nb * (H / R), NTHR, lds, s>>>(dout, wsp, din, Nb, H, pad);
+  if (!raise_lds<&conv_dgrad3_direct<CIN, NT, LW, KS, NTHR, PL>>((int)lds)) return SD_EARG;
+  conv_dgrad3_direct<CIN, NT, LW, KS, NTHR, PL><<<Nb * (H / R), NTHR, lds, s>>>(dout, amax, wsp, din, Nb, H, pad);
   SD_LAUNCH_CHECK();
   return SD_OK;
+}
+// the two shapes of the direct bwd-data kernel (Ci = dOut's channels, Co = dIn's): 1 = 48 -> 32 at 32 x 32 images as
+// 512-pixel tiles (16 rows) over 8 waves, one workgroup per CU; 2 = 64 -> 48 at 16 x 16 as whole-image 256-pixel tiles
+// over 4 waves (183 -> 131 us alone against 128-pixel tiles of 32-pixel waves, profiles/r06dg3); 0 = neither
+int dgrad_direct_shape(int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad) {
+  if (kh != 5 || kw != 5 || pad != 2 || Hs != Ws) return 0;
+  return Ci == 48 && Co == 32 && Ws == 32 ? 1 : Ci == 64 && Co == 48 && Ws == 16 ? 2 : 0;
+}
+template <bool PL>
+int dgrad_direct(const float* dout, const uint8_t* amax, const void* wsplit, float* din, int Nb, int Hs, int Ws, int Ci,
+                 int Co, int kh, int kw, int pad, hipStream_t s) {
+  const __bf16* wsp = static_cast<const __bf16*>(wsplit);
+  switch (dgrad_direct_shape(Hs, Ws, Ci, Co, kh, kw, pad)) {
+    case 1: return dgrad_direct_launch<48, 2, 5, 16, 512, PL>(dout, amax, wsp, din, Nb, Hs, pad, s);
+    case 2: return dgrad_direct_launch<64, 3, 4, 16, 256, PL>(dout, amax, wsp, din, Nb, Hs, pad, s);
+    default: return SD_ESHAPE;
+  }
 }
 }  // namespace
 
@@ -2347,13 +2445,25 @@ extern "C" int sd_conv2d_dgrad_direct(const float* dout, const void* wsplit, flo
   if (Nb <= 0) return SD_OK;
   if (kh != 5 || kw != 5 || pad != 2 || Hs != Ws || !aligned16(dout) || !aligned16(wsplit) || !aligned16(din))
     return SD_ESHAPE;
-  const __bf16* wsp = static_cast<const __bf16*>(wsplit);
-  // 32 x 32 images: 512-pixel tiles (16 rows) over 8 waves, one workgroup per CU
-  if (Ci == 48 && Co == 32 && Ws == 32) return dgrad_direct_launch<48, 2, 5, 16, 512>(dout, wsp, din, Nb, Hs, pad, s);
-  // 16 x 16 images: whole-image 256-pixel tiles over 4 waves (183 -> 131 us alone against 128-pixel tiles of 32-pixel
-  // waves, profiles/r06dg3)
-  if (Ci == 64 && Co == 48 && Ws == 16) return dgrad_direct_launch<64, 3, 4, 16, 256>(dout, wsp, din, Nb, Hs, pad, s);
-  return SD_ESHAPE;
+  return dgrad_direct<false>(dout, nullptr, wsplit, din, Nb, Hs, Ws, Ci, Co, kh, kw, pad, s);
+}
+
+// sd_conv2d_dgrad_direct of a pooled stage from (dpool, argmax): din (Nb, Hs, Ws, Co) = that entry's on
+// expand(dpool, amax), bit for bit, for the same two shapes (Hs, Ws: the full resolution; dpool and amax are
+// (Nb, Hs / 2, Ws / 2, Ci)). _ok: 1 where the shape is taken.
+extern "C" int sd_conv2d_dgrad_direct_pooled_ok(int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad) {
+  return dgrad_direct_shape(Hs, Ws, Ci, Co, kh, kw, pad) != 0;
+}
+extern "C" int sd_conv2d_dgrad_direct_pooled(const float* dpool, const uint8_t* amax, const void* wsplit, float* din,
+                                             int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad,
+                                             sd_stream stream_) {
+  if (!sd_conv2d_dgrad_direct_pooled_ok(Hs, Ws, Ci, Co, kh, kw, pad)) return SD_ESHAPE;
+  if (Nb <= 0) return SD_OK;
+  // amax is read as uint32 words (4 channels' argmax bytes per load)
+  if (!dpool || !amax || !wsplit || !din || !aligned16(dpool) || !aligned16(wsplit) || !aligned16(din) ||
+      reinterpret_cast<uintptr_t>(amax) % 4)
+    return SD_EARG;
+  return dgrad_direct<true>(dpool, amax, wsplit, din, Nb, Hs, Ws, Ci, Co, kh, kw, pad, (hipStream_t)stream_);
 }
 
 extern "C" int sd_conv2d_wgrad_bf16x3_slabs(int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int ups) {
@@ -2391,6 +2501,28 @@ extern "C" int sd_conv2d_wgrad_bf16x3(const float* in, const float* dout, float*
   if (!direct3_plan(Nb, Hs, Ws, Ci, Co, kh, kw, 0, pl) || !aligned16(in) || !aligned16(dout)) return SD_ESHAPE;
   return wgrad_direct<true>(in, dout, nullptr, dw_db, workspace, ws_floats, Nb, Hs, Ws, Ci, Co, kh, kw, pad, pl,
                             s, acc);
+}
+
+// sd_conv2d_wgrad_bf16x3 of a pooled stage from (dpool, argmax): direct3_plan's own plan (the same rung, R, gx and
+// slabs as on the full-resolution gradient) with dy expanded while it is staged, so the same values reach the same LDS
+// slots and [dW | db] is that entry's on expand(dpool, amax) bit for bit. H even on top of the plan (W is a power of
+// two >= 8); the query answers 0 outside it.
+extern "C" int sd_conv2d_wgrad_bf16x3_pooled_slabs(int Nb, int H, int W, int Ci, int Co, int kh, int kw) {
+  DirectPlan pl;
+  if (H % 2 || !direct3_plan(Nb, H, W, Ci, Co, kh, kw, 0, pl)) return 0;
+  return pl.slabs;
+}
+extern "C" int sd_conv2d_wgrad_bf16x3_pooled(const float* in, const float* dpool, const uint8_t* amax, float* dw_db,
+                                             float* workspace, long ws_floats, int Nb, int H, int W, int Ci, int Co,
+                                             int kh, int kw, int pad, const sd_wgrad_acc* acc_p, sd_stream stream_) {
+  if (Nb <= 0) return SD_OK;
+  sd_wgrad_acc acc;
+  if (!wgrad_acc_arg(acc_p, Ci, acc)) return SD_EARG;
+  DirectPlan pl;
+  if (H % 2 || !direct3_plan(Nb, H, W, Ci, Co, kh, kw, 0, pl)) return SD_ESHAPE;
+  if (!aligned16(dpool) || !aligned16(in) || !amax || reinterpret_cast<uintptr_t>(amax) % 4) return SD_EARG;
+  return wgrad_direct<true>(in, dpool, amax, dw_db, workspace, ws_floats, Nb, H, W, Ci, Co, kh, kw, pad, pl,
+                            (hipStream_t)stream_, acc);
 }
 
 // ---------------------------------------------------------------- first-stage input gradient from the pooled gradient

@@ -712,6 +712,65 @@ def conv2d_dgrad_pool(dpool, amax, w, pad=None):
     return din
 
 
+def conv2d_wgrad_pooled_slabs(x, Co, kh, kw):
+    """> 0 when the split-bf16 bwd-weight has its pooled-gradient form (sd_conv2d_wgrad_bf16x3_pooled) at this stage's
+    plan: the shapes conv2d_wgrad(fast=True) runs on the split-bf16 direct kernel, with H even."""
+    Nb, H, W, Ci = x.shape
+    if not FAST_GEMM:
+        return 0
+    return nat.fns["sd_conv2d_wgrad_bf16x3_pooled_slabs"](Nb, H, W, Ci, Co, kh, kw)
+
+
+def conv2d_wgrad_pooled(x, dpool, amax, kh, kw, pad=None, acc=None):
+    """conv2d_wgrad(x, expand(dpool, amax), fast=True) bit for bit, from the max-pool backward's pooled-resolution
+    gradient and the forward's argmax: the same kernel rung at the same plan expands them while staging. Raises where
+    conv2d_wgrad_pooled_slabs answers 0 (the caller asks first)."""
+    Nb, H, W, Ci = x.shape
+    Co = dpool.shape[-1]
+    _chk(x, dpool, amax)
+    if amax.shape != dpool.shape or amax.dtype != torch.uint8 or tuple(dpool.shape[:3]) != (Nb, H // 2, W // 2):
+        raise ValueError(f"conv2d_wgrad_pooled: x {tuple(x.shape)}, dpool {tuple(dpool.shape)}, amax "
+                         f"{tuple(amax.shape)} {amax.dtype}")
+    pad = (kh - 1) // 2 if pad is None else pad
+    ks = conv2d_wgrad_pooled_slabs(x, Co, kh, kw)
+    if ks <= 0:
+        raise nat.NativeError("sd_conv2d_wgrad_bf16x3_pooled: shape outside the split-bf16 direct plan")
+    return _wgrad_call("sd_conv2d_wgrad_bf16x3_pooled", ks, (Co, kh * kw * Ci, x.device), acc,
+                       (p(_c(x)), p(_c(dpool)), p(_c(amax))), (Nb, H, W, Ci, Co, kh, kw, pad))
+
+
+def conv2d_dgrad_pooled_takes(H, W, Co, Ci, kh, kw, pad=None):
+    """True when conv2d_dgrad_pooled (sd_conv2d_dgrad_direct_pooled) handles this stage's shape: x (.., H, W, Ci),
+    w (Co, kh, kw, Ci)."""
+    pad = kh - 1 - (kh - 1) // 2 if pad is None else pad
+    return FAST_GEMM and nat.fns["sd_conv2d_dgrad_direct_pooled_ok"](H, W, Co, Ci, kh, kw, pad) > 0
+
+
+def conv2d_dgrad_pooled(dpool, amax, w, pad=None):
+    """conv2d_dgrad(expand(dpool, amax), w) bit for bit on the direct split-bf16 kernel, from the pooled-resolution
+    gradient dpool (Nb, H/2, W/2, Co) and the forward's argmax: the expanded gradient exists in LDS only. None when the
+    shape is outside the kernel's two (conv2d_dgrad_pooled_takes)."""
+    Nb, Ho, Wo, Co = dpool.shape
+    _, kh, kw, Ci = w.shape
+    _chk(dpool, amax, w)
+    if amax.shape != dpool.shape or amax.dtype != torch.uint8 or w.shape[0] != Co:
+        raise ValueError(f"conv2d_dgrad_pooled: dpool {tuple(dpool.shape)}, amax {tuple(amax.shape)} {amax.dtype}, "
+                         f"w {tuple(w.shape)}")
+    pad = kh - 1 - (kh - 1) // 2 if pad is None else pad
+    H, W = 2 * Ho, 2 * Wo
+    if not conv2d_dgrad_pooled_takes(H, W, Co, Ci, kh, kw, pad):
+        return None
+    ws = _SPLIT.get(w.data_ptr())
+    if ws is None:
+        wf = _FLIP.get(w.data_ptr())
+        ws = conv_split_weight(conv_flip_weight(w) if wf is None else wf)
+    din = torch.empty(Nb, H, W, Ci, dtype=torch.float32, device=dpool.device)
+    if not nat.call_shaped("sd_conv2d_dgrad_direct_pooled", p(_c(dpool)), p(_c(amax)), p(ws), p(din), Nb, H, W, Co, Ci,
+                           kh, kw, pad, stream()):
+        return None
+    return din
+
+
 # ------------------------------------------------------------------------------------------------- adversarial patch
 _PATCH_CHUNK = nat._define(nat.HEADER, "SD_PATCH_CHUNK")
 

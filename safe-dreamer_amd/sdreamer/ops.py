@@ -307,7 +307,7 @@ def block_linear(x, wp, b):
 
 
 # ------------------------------------------------------------------------------------------------- conv
-# SDREAMER_POOL_COMPACT=0: first-stage backward through the full-resolution conv gradient (benchmark / test knob)
+# SDREAMER_POOL_COMPACT=0: every stage's backward through the full-resolution conv gradient (benchmark / test knob)
 POOL_COMPACT = os.environ.get("SDREAMER_POOL_COMPACT", "1") != "0"
 
 
@@ -363,15 +363,27 @@ def _pooled_dx(ctx, x, w):
             and k.conv2d_dgrad_pool_takes(H, W, Co, Ci, kh, kw))
 
 
-def _stage_dx(ctx, x, w, dconv, dpool, amax):
+def _pooled_x3(ctx, x, w):
+    """True when the stage's backward runs the split-bf16 contractions from the pooled gradient (k.conv2d_wgrad_pooled,
+    k.conv2d_dgrad_pooled): its bwd-weight has the pooled form at its plan, and its input gradient is not wanted or has
+    one too. The full-resolution conv gradient (3/4 zeros) is then never written or read; every gradient is the
+    full-resolution route's bit for bit."""
+    Nb, H, W, Cx = x.shape
+    Co, kh, kw, Ci = w.shape
+    if not POOL_COMPACT or k.conv2d_wgrad_pooled_slabs(x, Co, kh, kw) <= 0:
+        return False
+    return not ctx.needs_input_grad[0] or (Cx == Ci and k.conv2d_dgrad_pooled_takes(H, W, Co, Ci, kh, kw))
+
+
+def _stage_dx(ctx, x, w, dconv, dpool, amax, x3=False):
     """The stage's input gradient in the shape autograd expects: the raw image's channels (pad_shift route) or x's.
-    dconv None: from the pooled gradient; else conv2d_dgrad, on the zero-padded weight when x carries pad channels
-    (their gradient is zero: they meet zero weights only)."""
+    dconv None: from the pooled gradient (x3: on the direct split-bf16 kernel); else conv2d_dgrad, on the zero-padded
+    weight when x carries pad channels (their gradient is zero: they meet zero weights only)."""
     Cx, Ci = x.shape[-1], w.shape[-1]
     if dconv is None:
-        dx = k.conv2d_dgrad_pool(dpool, amax, w)
+        dx = k.conv2d_dgrad_pooled(dpool, amax, w) if x3 else k.conv2d_dgrad_pool(dpool, amax, w)
         if dx is None:
-            raise k.nat.NativeError("sd_conv2d_dgrad_pool refused a shape its query accepted")
+            raise k.nat.NativeError("the pooled input gradient refused a shape its query accepted")
     else:
         dx = k.conv2d_dgrad(dconv, w if Cx == Ci else _pad_last(w, Cx))
     want = ctx.raw_c if ctx.raw_c is not None else Cx
@@ -380,6 +392,22 @@ def _stage_dx(ctx, x, w, dconv, dpool, amax):
     elif dx.shape[-1] < want:
         dx = _pad_last(dx, want)
     return dx
+
+
+def _stage_wgrad(x, dconv, dpool, amax, kh, kw, acc):
+    """The stage's split-bf16 bwd-weight, from the full-resolution conv gradient or (dpool set) from the pooled one;
+    queued while ops.defer_wgrads is active (only the data gradient continues the backward chain). Neither given: the
+    first stage's pooled route has run its own already."""
+    if dconv is None and dpool is None:
+        return
+    if dpool is not None:
+        wgrad, keep = (lambda: k.conv2d_wgrad_pooled(x, dpool, amax, kh, kw, acc=acc)), (x, dpool, amax)
+    else:
+        wgrad, keep = (lambda: k.conv2d_wgrad(x, dconv, kh, kw, acc=acc)), (x, dconv)
+    if _DEFER is not None:
+        _DEFER.append((wgrad, keep))
+    else:
+        wgrad()
 
 
 class ConvPoolNormFn(torch.autograd.Function):
@@ -411,27 +439,23 @@ class ConvPoolNormFn(torch.autograd.Function):
         Co, kh, kw, Ci = w.shape
         acc = (grad_buf(w), grad_buf(b), Ci)  # the bwd-weight launches add into the gradients themselves
         dpool = None
-        if _pooled_dx(ctx, x, w) or (not ctx.needs_input_grad[0] and POOL_COMPACT and
-                                     k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0):
+        first = _pooled_dx(ctx, x, w) or (not ctx.needs_input_grad[0] and POOL_COMPACT and
+                                          k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0)
+        x3 = not first and _pooled_x3(ctx, x, w)
+        if first:
             # first stage: the bwd-weight kernel (and the input-gradient kernel, when the image's gradient is wanted)
             # expands the pooled gradient + argmax itself, so the full-resolution conv gradient (3/4 zeros) is never
             # written or read
             dpool = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw), nchw_flat=ctx.nchw_flat)
             k.conv2d_wgrad_pool(x, dpool, amax, kh, kw, acc=acc)
             dconv = None
+        elif x3:  # later stages: the same, on the split-bf16 kernels of the full-resolution route (bit-identical)
+            dpool = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw), nchw_flat=ctx.nchw_flat)
+            dconv = None
         else:
             dconv = k.pool_rms_bwd(pooled, amax, nw, rstd, dy.contiguous(), H, W, grad_buf(nw), nchw_flat=ctx.nchw_flat)
-
-        def wgrad():
-            k.conv2d_wgrad(x, dconv, kh, kw, acc=acc)
-
-        if dconv is None:
-            pass
-        elif _DEFER is not None:  # queued: only the data gradient continues the backward chain
-            _DEFER.append((wgrad, (x, dconv)))
-        else:
-            wgrad()
-        dx = _stage_dx(ctx, x, w, dconv, dpool, amax) if ctx.needs_input_grad[0] else None
+        _stage_wgrad(x, dconv, dpool if x3 else None, amax, kh, kw, acc)
+        dx = _stage_dx(ctx, x, w, dconv, dpool, amax, x3) if ctx.needs_input_grad[0] else None
         return dx, None, None, None, None, None
 
 
@@ -467,26 +491,23 @@ class FilmConvPoolNormFn(torch.autograd.Function):
         acc = (grad_buf(w), grad_buf(b), Ci)
         film = (gamma, beta)
         dpool = None
-        if _pooled_dx(ctx, x, w) or (not ctx.needs_input_grad[0] and POOL_COMPACT and
-                                     k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0):
+        first = _pooled_dx(ctx, x, w) or (not ctx.needs_input_grad[0] and POOL_COMPACT and
+                                          k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0)
+        x3 = not first and _pooled_x3(ctx, x, w)
+        if first:
             dpool, dgamma, dbeta = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw),
                                                           nchw_flat=ctx.nchw_flat, film=film)
             k.conv2d_wgrad_pool(x, dpool, amax, kh, kw, acc=acc)
             dconv = None
+        elif x3:
+            dpool, dgamma, dbeta = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw),
+                                                          nchw_flat=ctx.nchw_flat, film=film)
+            dconv = None
         else:
             dconv, dgamma, dbeta = k.pool_rms_bwd(pooled, amax, nw, rstd, dy.contiguous(), H, W, grad_buf(nw),
                                                   nchw_flat=ctx.nchw_flat, film=film)
-
-        def wgrad():
-            k.conv2d_wgrad(x, dconv, kh, kw, acc=acc)
-
-        if dconv is None:
-            pass
-        elif _DEFER is not None:
-            _DEFER.append((wgrad, (x, dconv)))
-        else:
-            wgrad()
-        dx = _stage_dx(ctx, x, w, dconv, dpool, amax) if ctx.needs_input_grad[0] else None
+        _stage_wgrad(x, dconv, dpool if x3 else None, amax, kh, kw, acc)
+        dx = _stage_dx(ctx, x, w, dconv, dpool, amax, x3) if ctx.needs_input_grad[0] else None
         return dx, None, None, None, dgamma, dbeta, None, None
 
 
