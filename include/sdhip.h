@@ -150,6 +150,9 @@ int sd_kl_bwd(const float* post, const float* prior, const float* kl_row, const 
 /* ---------------------------------------------------------------- heads
  * symexp two-hot (TwoHot, distributions.py:67-129; symexp_twohot bins 242-251): mode, log_prob fwd/bwd. NB odd <= 255 */
 int sd_twohot_mode(const float* logits, const float* bins, float* out, long rows, int NB, sd_stream stream);
+/* d mode / d logits: dlogits[r, j] = p[r, j] (bins[j] - mode[r]) dout[r]; mode summed as sd_twohot_mode sums it */
+int sd_twohot_mode_bwd(const float* logits, const float* bins, const float* dout, float* dlogits, long rows, int NB,
+                       sd_stream stream);
 int sd_twohot_logp_fwd(const float* logits, const float* bins, const float* target, float* logp, long rows, int NB,
                        sd_stream stream);
 int sd_twohot_logp_bwd(const float* logits, const float* bins, const float* target, const float* glogp,
@@ -180,6 +183,11 @@ int sd_imag_ac_loss_bwd(const float* vl, const float* bins, const float* ret, co
 /* bounded normal actor (bounded_normal, distributions.py:217-222): x (rows, 2A) = [mean | std-logit] */
 int sd_bnormal_sample(const float* x, float* action, long rows, int A, float min_std, float max_std, uint64_t seed,
                       int stream_id, int step, long row_offset, const uint64_t* seed_ptr, sd_stream stream);
+/* reparameterised gradient of the sample: d_action_norm (rows, A) is the gradient of action / max(|action|, 1) (the
+ * divisor a constant, rssm.py:44), dx (rows, 2A) that of [mean | std-logit]; eps from sd_bnormal_sample's counters */
+int sd_bnormal_sample_bwd(const float* d_action_norm, const float* x, const float* action, float* dx, long rows,
+                          int A, float min_std, float max_std, uint64_t seed, int stream_id, int step,
+                          long row_offset, const uint64_t* seed_ptr, sd_stream stream);
 int sd_bnormal_logp_ent_fwd(const float* x, const float* action, float* logp, float* ent, long rows, int A,
                             float min_std, float max_std, sd_stream stream);
 int sd_bnormal_logp_ent_bwd(const float* x, const float* action, const float* glogp, const float* gent, float* dx,
@@ -214,6 +222,15 @@ int sd_lambda_return_strided(const float* reward, long rew_row_stride, long rew_
                              const float* cont_logit, long cont_row_stride, long cont_t_stride, const float* last,
                              const float* boot, long boot_row_stride, long boot_t_stride, float* ret, float* cont,
                              float* weight, int N, int T, float disc, float lamb, sd_stream stream);
+/* Backward of the imagination case (term = 1 - sigmoid(cont_logit), last = 0, boot = value): d_ret (N, T-1) row-major
+ * -> d_reward, d_value, d_cont_logit (the sigmoid folded in), each written at [r*out_row_stride + t*out_t_stride],
+ * column t = 0 zero. reward / cont_logit / value are the forward's, read through (row, t) strides. One lane per row,
+ * a forward-time recurrence in a fixed order. */
+int sd_lambda_return_bwd(const float* d_ret, const float* reward, long rew_row_stride, long rew_t_stride,
+                         const float* cont_logit, long cont_row_stride, long cont_t_stride, const float* value,
+                         long val_row_stride, long val_t_stride, float* d_reward, float* d_value,
+                         float* d_cont_logit, long out_row_stride, long out_t_stride, int N, int T, float disc,
+                         float lamb, sd_stream stream);
 /* ReturnEMA (networks.py:406-422): torch.quantile(x, [q0, q1]) (exact radix select + lerp), ema <- alpha q +
  * (1-alpha) ema, offset_scale = (ema[0], max(ema[1]-ema[0], 1)). quantiles (2) optional. */
 int sd_return_ema(const float* x, int n, float* ema, float* offset_scale, float* quantiles, float alpha, float q0,

@@ -232,6 +232,37 @@ __global__ void twohot_mode_kernel(const float* __restrict__ logits, const float
   if (lane == 0) out[r] = sp[wave][c] * bins[c] + acc;
 }
 
+// d mode / d logits[j] = p[j] (bins[j] - mode), times the row's upstream gradient; mode summed in twohot_mode_kernel's
+// order (the +- bin pairs), so both kernels hold the same value
+__global__ void twohot_mode_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ bins,
+                                       const float* __restrict__ dout, float* __restrict__ dlogits, long rows, int NB) {
+  __shared__ float sp[4][256];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + wave;
+  if (r >= rows) return;
+  float p[4], lse;
+  row_softmax64(logits + r * NB, NB, p, lse, lane);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) sp[wave][lane + 64 * j] = p[j];
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  const int c = (NB - 1) / 2;
+  float acc = 0.f;
+  for (int i = lane; i < c; i += 64) {
+    const float lo = sp[wave][c - 1 - i] * bins[c - 1 - i];
+    const float hi = sp[wave][c + 1 + i] * bins[c + 1 + i];
+    acc += lo + hi;
+  }
+  acc = wave_sum(acc);
+  const float mode = sp[wave][c] * bins[c] + acc;
+  const float d = dout[r];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = lane + 64 * j;
+    if (col < NB) dlogits[r * NB + col] = p[j] * (bins[col] - mode) * d;
+  }
+}
+
 SD_DEV void twohot_target(const float* bins, int NB, float t, int& below, int& above, float& wb, float& wa, int lane) {
   // below = #(bins <= t) - 1, above = NB - #(bins > t), clamped (distributions.py:106-109)
   int cle = 0, cgt = 0;
@@ -453,6 +484,25 @@ __global__ void bnormal_sample(const float* __restrict__ x, float* __restrict__ 
   action[t] = loc + eps * sc;
 }
 
+// Reparameterised gradient of the sampled, normalised action a / max(|a|, 1) (the divisor a constant, rssm.py:44):
+// a = loc + eps sc, so d loc = d a and d sc = d a eps, eps drawn again from bnormal_sample's Philox counters.
+__global__ void bnormal_sample_bwd(const float* __restrict__ d_an, const float* __restrict__ x,
+                                   const float* __restrict__ action, float* __restrict__ dx, long rows, int A,
+                                   float min_std, float max_std, uint64_t seed, uint32_t stream, uint32_t step,
+                                   long row_offset, const uint64_t* seed_ptr) {
+  if (seed_ptr) seed += *seed_ptr;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= rows * A) return;
+  const long r = t / A;
+  const int j = (int)(t % A);
+  const float loc = tanhf(x[r * 2 * A + j]);
+  const float sg = sigmoidf_(x[r * 2 * A + A + j] + 2.f);
+  const float eps = sd_normal(seed, stream, step, (uint64_t)(r + row_offset) * A + j);
+  const float da = d_an[t] / fmaxf(fabsf(action[t]), 1.f);
+  dx[r * 2 * A + j] = da * (1.f - loc * loc);
+  dx[r * 2 * A + A + j] = da * eps * (max_std - min_std) * sg * (1.f - sg);
+}
+
 __global__ void bnormal_logp_ent_fwd(const float* __restrict__ x, const float* __restrict__ action,
                                      float* __restrict__ logp, float* __restrict__ ent, long rows, int A, float min_std,
                                      float max_std) {
@@ -648,6 +698,15 @@ extern "C" int sd_twohot_mode(const float* logits, const float* bins, float* out
   return SD_OK;
 }
 
+extern "C" int sd_twohot_mode_bwd(const float* logits, const float* bins, const float* dout, float* dlogits, long rows,
+                                  int NB, sd_stream s) {
+  if (rows <= 0) return SD_OK;
+  if (NB > 255 || NB < 1 || NB % 2 == 0) return SD_ESHAPE;
+  twohot_mode_bwd_kernel<<<blocks_for(rows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, dout, dlogits, rows, NB);
+  SD_LAUNCH_CHECK();
+  return SD_OK;
+}
+
 extern "C" int sd_twohot_logp_fwd(const float* logits, const float* bins, const float* target, float* logp, long rows,
                                   int NB, sd_stream s) {
   if (rows <= 0) return SD_OK;
@@ -721,6 +780,16 @@ extern "C" int sd_bnormal_sample(const float* x, float* action, long rows, int A
   if (rows <= 0) return SD_OK;
   bnormal_sample<<<blocks_for(rows * A, 256), 256, 0, (hipStream_t)s>>>(x, action, rows, A, min_std, max_std, seed,
                                                                         stream_id, step, row_offset, seed_ptr);
+  SD_LAUNCH_CHECK();
+  return SD_OK;
+}
+
+extern "C" int sd_bnormal_sample_bwd(const float* d_action_norm, const float* x, const float* action, float* dx,
+                                     long rows, int A, float min_std, float max_std, uint64_t seed, int stream_id,
+                                     int step, long row_offset, const uint64_t* seed_ptr, sd_stream s) {
+  if (rows <= 0 || A <= 0) return SD_OK;
+  bnormal_sample_bwd<<<blocks_for(rows * A, 256), 256, 0, (hipStream_t)s>>>(
+      d_action_norm, x, action, dx, rows, A, min_std, max_std, seed, stream_id, step, row_offset, seed_ptr);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }

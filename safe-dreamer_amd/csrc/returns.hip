@@ -116,6 +116,52 @@ __global__ __launch_bounds__(256) void lambda_return_staged(const float* __restr
   }
 }
 
+// Backward of the imagination case (term = 1 - sigmoid(cont_logit), last = 0, boot = value):
+//   ret[t] = reward[i] + c[i] disc ((1 - lamb) value[i] + lamb ret[t + 1]),  i = t + 1,  ret[T - 1] := value[T - 1].
+// The reverse-time recurrence's adjoint runs forward in time: G[0] = d_ret[0], G[t] = d_ret[t] + G[t - 1] c[t] disc lamb.
+// One lane per row, fixed order, no atomics. ret is recomputed first (the forward's arithmetic and order) and parked
+// in the row's d_value slots, each read back just before its slot takes the gradient. in: (row, t) strides of
+// reward / cont_logit / value; out: (row, t) strides shared by the three outputs; column 0 of every output is 0.
+struct LrbStrides {
+  long rew_r, rew_t, cont_r, cont_t, val_r, val_t, out_r, out_t;
+};
+
+__global__ void lambda_return_bwd_kernel(const float* __restrict__ d_ret, const float* __restrict__ reward,
+                                         const float* __restrict__ cont_logit, const float* __restrict__ value,
+                                         LrbStrides rs, float* __restrict__ d_reward, float* d_value,
+                                         float* __restrict__ d_cont_logit, int N, int T, float disc, float lamb) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= N) return;
+  const long ob = (long)r * rs.out_r;
+  const float v_last = value[r * rs.val_r + (long)(T - 1) * rs.val_t];
+  float out = v_last;
+  for (int t = T - 2; t >= 0; --t) {
+    const int i = t + 1;
+    const float term = 1.f - sigmoidf_(cont_logit[r * rs.cont_r + i * rs.cont_t]);
+    const float live = (1.f - term) * disc;
+    const float cnt = lamb;
+    const float interm = reward[r * rs.rew_r + i * rs.rew_t] + (1.f - cnt) * live * value[r * rs.val_r + i * rs.val_t];
+    out = interm + live * cnt * out;
+    d_value[ob + t * rs.out_t] = out;  // ret[t], parked
+  }
+  d_reward[ob] = 0.f;
+  d_cont_logit[ob] = 0.f;
+  float carry = 0.f;  // G[t - 1] c[t] disc lamb
+  for (int t = 0; t <= T - 2; ++t) {
+    const int i = t + 1;
+    const float c = sigmoidf_(cont_logit[r * rs.cont_r + i * rs.cont_t]);
+    const float live = c * disc;
+    const float v = value[r * rs.val_r + i * rs.val_t];
+    const float next = i <= T - 2 ? d_value[ob + i * rs.out_t] : v_last;  // ret[t + 1]
+    const float g = d_ret[(long)r * (T - 1) + t] + carry;
+    carry = g * (live * lamb);
+    d_reward[ob + i * rs.out_t] = g;
+    d_value[ob + i * rs.out_t] = i == T - 1 ? g * live : g * ((1.f - lamb) * live);
+    d_cont_logit[ob + i * rs.out_t] = g * disc * ((1.f - lamb) * v + lamb * next) * (c * (1.f - c));
+  }
+  d_value[ob] = 0.f;
+}
+
 SD_DEV uint32_t fkey(float f) {
   const uint32_t b = __float_as_uint(f);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
@@ -243,6 +289,21 @@ extern "C" int sd_lambda_return(const float* reward, const float* term, const fl
                                 float* weight, int N, int T, float disc, float lamb, sd_stream s) {
   return sd_lambda_return_strided(reward, T, 1, term, cont_logit, T, 1, last, boot, boot_row_stride, boot_t_stride, ret,
                                   cont, weight, N, T, disc, lamb, s);
+}
+
+extern "C" int sd_lambda_return_bwd(const float* d_ret, const float* reward, long rew_row_stride, long rew_t_stride,
+                                    const float* cont_logit, long cont_row_stride, long cont_t_stride,
+                                    const float* value, long val_row_stride, long val_t_stride, float* d_reward,
+                                    float* d_value, float* d_cont_logit, long out_row_stride, long out_t_stride, int N,
+                                    int T, float disc, float lamb, sd_stream s) {
+  if (N <= 0 || T <= 0) return SD_OK;
+  if (!d_ret || !reward || !cont_logit || !value || !d_reward || !d_value || !d_cont_logit) return SD_EARG;
+  const LrbStrides rs{rew_row_stride, rew_t_stride, cont_row_stride, cont_t_stride,
+                      val_row_stride, val_t_stride, out_row_stride, out_t_stride};
+  lambda_return_bwd_kernel<<<(N + 63) / 64, 64, 0, (hipStream_t)s>>>(d_ret, reward, cont_logit, value, rs, d_reward,
+                                                                    d_value, d_cont_logit, N, T, disc, lamb);
+  SD_LAUNCH_CHECK();
+  return SD_OK;
 }
 
 extern "C" int sd_return_ema(const float* x, int n, float* ema, float* offset_scale, float* quantiles, float alpha,

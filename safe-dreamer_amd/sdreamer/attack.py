@@ -1,14 +1,15 @@
-"""Posterior-level adversarial patch: a small image patch optimised through the encoder and the RSSM posterior.
+"""Adversarial patch: a small image patch optimised through the encoder, the RSSM posterior and the imagination.
 
 The patch is pasted into every frame of a batch (csrc/attack.hip: sd_patch_apply), the world model's posterior of the
-patched frames is compared with the posterior of the clean frames (PosteriorAttackLoss), the loss is differentiated to
-the image (Dreamer.posterior(with_grad=True): the first encoder stage's input gradient is sd_conv2d_dgrad_pool), folded
-back onto the patch (sd_patch_grad) and one Adam step + projection is taken (sd_patch_step). The planning-level term of
-the attack, the imagined return differentiated through the imagination rollout, needs a backward of the fused
-imagination kernels, which are no_grad by design: `w_return` is refused.
+patched frames is compared with the posterior of the clean frames (PosteriorAttackLoss) and, with `w_return`, rolled
+out by the frozen actor to its imagined lambda-return (PlanningAttackLoss: Dreamer.imagined_return, whose backward is
+ops.ImagineReturnFn). The loss is differentiated to the image (Dreamer.posterior(with_grad=True): the first encoder
+stage's input gradient is sd_conv2d_dgrad_pool), folded back onto the patch (sd_patch_grad) and one Adam step +
+projection is taken (sd_patch_step). DESIGN.md §4.4c.
 
     from sdreamer.attack import load_attack_config, train_patch
     patch, log = train_patch(agent, [(data, initial), ...], load_attack_config(["steps=200", "w_action=1.0"]))
+    patch, log = train_patch(agent, batches, load_attack_config(["w_return=1.0", "w_kl=0.0"]))  # upstream's default
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ from .config import load_config
 
 PLACEMENTS = ("bottom_center", "top_center", "center", "fixed", "saliency")
 LOG_KEYS = ("loss", "kl", "action", "tv")
+LOG_KEYS_PLANNING = LOG_KEYS + ("ret",)  # the log's columns with w_return != 0
 SALIENCY_SIGMA = 0.05  # the seeded image perturbation at which the saliency gradient is taken
 
 
@@ -142,7 +144,8 @@ class PosteriorAttackLoss:
         if float(w_return) != 0.0:
             raise NotImplementedError(
                 "w_return: the imagined-return term needs a backward through the imagination rollout, and the fused "
-                "imagination kernels (sd_imagine) are forward-only (no_grad by design); see DESIGN.md §7")
+                "imagination kernels (sd_imagine) are forward-only (no_grad by design): PlanningAttackLoss has that "
+                "term (Dreamer.imagined_return); see DESIGN.md §4.4c")
         self.w_kl, self.w_action, self.w_tv = float(w_kl), float(w_action), float(w_tv)
 
     def actor_mode(self, agent, post_stoch, post_deter):
@@ -173,6 +176,46 @@ class PosteriorAttackLoss:
         return -(self.w_kl * kl + self.w_action * act), {"kl": kl.detach(), "action": act.detach()}
 
 
+class PlanningAttackLoss:
+    """loss = w_return * mean(ret0) - (w_kl * KL + w_action * shift): minimising it lowers the agent's imagined
+    return. ret0 (B * T,): Dreamer.imagined_return from every patched posterior state, `horizon` steps (None: the
+    agent's imag_horizon), the imagination's noise from the batch's seed. KL, shift and clean() are
+    PosteriorAttackLoss's; w_tv as there."""
+
+    def __init__(self, w_return=1.0, w_kl=0.0, w_action=0.0, w_tv=0.01, horizon=None):
+        self.posterior = PosteriorAttackLoss(w_kl, w_action, w_tv)
+        self.w_return, self.w_kl, self.w_action, self.w_tv = float(w_return), float(w_kl), float(w_action), float(w_tv)
+        self.horizon = None if horizon is None else int(horizon)
+
+    def clean(self, agent, post):
+        return self.posterior.clean(agent, post)
+
+    def __call__(self, agent, clean, post_stoch, post_deter, post_logit, seed=0):
+        """-> (loss, {"kl": ..., "action": ..., "ret": mean(ret0)}) as 0-dim device tensors"""
+        total, terms = self.posterior(agent, clean, post_stoch, post_deter, post_logit)
+        if self.w_return:
+            ret = agent.imagined_return(post_stoch, post_deter, self.horizon, seed=seed).mean()
+            total = self.w_return * ret + total
+        else:
+            ret = torch.zeros((), dtype=torch.float32, device=post_logit.device)
+        terms["ret"] = ret.detach()
+        return total, terms
+
+
+def make_loss(cfg):
+    """The objective a configuration asks for: PlanningAttackLoss with w_return != 0, else PosteriorAttackLoss"""
+    w_return = float(cfg.get("w_return", 0.0))
+    if w_return != 0.0:
+        return PlanningAttackLoss(w_return, cfg.w_kl, cfg.w_action, cfg.w_tv, cfg.get("horizon", None))
+    return PosteriorAttackLoss(cfg.w_kl, cfg.w_action, cfg.w_tv, w_return)
+
+
+def _evaluate(loss, agent, clean, post, seed):
+    if isinstance(loss, PlanningAttackLoss):
+        return loss(agent, clean, *post, seed=seed)
+    return loss(agent, clean, *post)
+
+
 # ------------------------------------------------------------------------------------------------- the loop
 def _tile(t, copies):
     return t if copies == 0 else t.repeat(1 + copies, *([1] * (t.dim() - 1)))
@@ -184,7 +227,8 @@ def _f32_image(img):
 
 def attack_gradient(agent, patch, loss, data, initial, seed, offsets, clean=None):
     """One evaluation of the objective on a batch with the patch at `offsets` (N * copies rows: the batch is tiled to
-    match): -> (loss, terms, d_image, clean). No parameter gradient is written (ops.grad_sink_scope)."""
+    match, and a PlanningAttackLoss imagines from the tiled rows): -> (loss, terms, d_image, clean). No parameter
+    gradient is written (ops.grad_sink_scope)."""
     B, T = data["action"].shape[:2]
     copies = offsets.shape[0] // (B * T) - 1
     tiled = {k: _tile(v, copies) for k, v in data.items() if k != "__enc_image"}
@@ -195,21 +239,22 @@ def attack_gradient(agent, patch, loss, data, initial, seed, offsets, clean=None
     img.requires_grad_(True)
     with ops.grad_sink_scope():
         post = agent.posterior({**tiled, "image": img}, init, seed=seed, with_grad=True)
-        total, terms = loss(agent, clean, *post)
+        total, terms = _evaluate(loss, agent, clean, post, seed)
         (d_image,) = torch.autograd.grad(total, img)
     return total.detach(), terms, d_image, clean
 
 
 def _saliency(agent, loss, data, initial, seed, patch_hw, generator):
     """|d objective / d image| summed over the batch, time and channels, taken at a seeded perturbation of the clean
-    frames (at the clean frames themselves both terms are stationary: the gradient is exactly zero)."""
+    frames (at the clean frames themselves the KL and action terms are stationary: their gradient is exactly zero;
+    the return term's is not, but the perturbation stays so that the placement does not depend on the weights)."""
     img = _f32_image(data["image"])
     noise = torch.randn(img.shape, generator=generator).to(img.device)
     pert = (img + SALIENCY_SIGMA * noise).clamp_(0.0, 1.0).requires_grad_(True)
     clean = loss.clean(agent, agent.posterior(data, initial, seed=seed))
     with ops.grad_sink_scope():
         post = agent.posterior({**data, "image": pert}, initial, seed=seed, with_grad=True)
-        total, _ = loss(agent, clean, *post)
+        total, _ = _evaluate(loss, agent, clean, post, seed)
         (g,) = torch.autograd.grad(total, pert)
     return saliency_offset(g.abs().sum(dim=(0, 1, 4)), patch_hw)
 
@@ -217,14 +262,16 @@ def _saliency(agent, loss, data, initial, seed, patch_hw, generator):
 def train_patch(agent, batches, cfg, patch=None):
     """Optimise a patch against `agent` on `batches` (a list of (data, initial); data a dict of (B, T, *) device
     tensors, image uint8 or f32) for cfg.steps steps -> (patch (ph, pw, C), log (steps, 4)): the objective's terms
-    per step in LOG_KEYS order, a device tensor (no host synchronisation in the loop). Step i uses batch i mod
+    per step in LOG_KEYS order (with cfg.w_return != 0: (steps, 5), LOG_KEYS_PLANNING, and the objective is
+    PlanningAttackLoss), a device tensor (no host synchronisation in the loop). Step i uses batch i mod
     len(batches) with the posterior noise of seed cfg.seed + that batch's index; its clean posterior is computed
     once."""
     if agent.rep_loss == "dreamerpro":
         raise NotImplementedError("the patch attack with rep_loss=dreamerpro")
     if getattr(agent, "world", 1) > 1:
         raise NotImplementedError("the patch attack under data parallel")
-    loss = PosteriorAttackLoss(cfg.w_kl, cfg.w_action, cfg.w_tv, cfg.get("w_return", 0.0))
+    loss = make_loss(cfg)
+    planning = isinstance(loss, PlanningAttackLoss)
     img0 = batches[0][0]["image"]
     B, T, H, W, C = img0.shape
     seed = int(cfg.get("seed", 0))
@@ -235,7 +282,8 @@ def train_patch(agent, batches, cfg, patch=None):
     if patch.placement == "saliency":
         patch.offset = _saliency(agent, loss, *batches[0], seed, patch.patch_hw, patch.generator)
     steps = int(cfg.steps)
-    log = torch.zeros(steps, len(LOG_KEYS), dtype=torch.float32, device=img0.device)
+    log = torch.zeros(steps, len(LOG_KEYS_PLANNING if planning else LOG_KEYS), dtype=torch.float32,
+                      device=img0.device)
     cleans = {}
     for i in range(steps):
         j = i % len(batches)
@@ -245,5 +293,7 @@ def train_patch(agent, batches, cfg, patch=None):
                                                            cleans.get(j))
         d_patch, tv = patch.grad(d_image, offsets, loss.w_tv)
         log[i, 0], log[i, 1], log[i, 2], log[i, 3] = total + loss.w_tv * tv[0], terms["kl"], terms["action"], tv[0]
+        if planning:
+            log[i, 4] = terms["ret"]
         patch.step(d_patch)
     return patch.patch, log

@@ -1271,7 +1271,8 @@ class Dreamer(nn.Module):
         # the value head's first layer on the imagined feats, the same contraction the value loss's forward needs
         # (_frozen_value aliases value; the weights change only at the optimizer step)
         val_h0 = firsts[0][2] if (firsts and REUSE_H0) else None
-        return dict(ret=ret, weight=weight, i_cont=i_cont, i_rew=i_rew, i_val=i_val, i_slow=i_slow, val_h0=val_h0)
+        return dict(ret=ret, weight=weight, i_cont=i_cont, i_rew=i_rew, i_val=i_val, i_slow=i_slow, val_h0=val_h0,
+                    i_contl=i_contl)
 
     @torch.no_grad()
     def _returns_norm(self, rr):
@@ -1460,6 +1461,18 @@ class Dreamer(nn.Module):
         """Reference-layout wrapper: (N, H1, F), (N, H1, A)."""
         f, a = self._imagine_tm(start, imag_horizon, seed, row_offset)
         return f.transpose(0, 1), a.transpose(0, 1)
+
+    def imagined_return(self, post_stoch, post_deter, horizon=None, seed=0, row_offset=0, keep=None):
+        """ret0 (N,): the lambda-return (dreamer.py:600) of the frozen actor's imagined rollout from the N start states
+        post_stoch (..., S, K) / post_deter (..., D) (N = the product of the leading dimensions), with the imagination's
+        noise streams and counters (`seed`, `row_offset`) and H1 = (horizon or imag_horizon) + 1 feats. Differentiable
+        in the start state only (ops.ImagineReturnFn): the actor, the RSSM and the heads are frozen, no parameter
+        gradient is written. keep (a dict): receives the rollout's feats, actions and ret (N, H)."""
+        H1 = (self.imag_horizon if horizon is None else int(horizon)) + 1
+        D = post_deter.shape[-1]
+        N = post_deter.numel() // D
+        return ops.ImagineReturnFn.apply(post_stoch.reshape(N, self.rssm._stoch, self.rssm._discrete),
+                                         post_deter.reshape(N, D), self, H1, seed, row_offset, keep)
 
     @torch.no_grad()
     def _lambda_return(self, last, term, reward, value, boot, disc, lamb):  # dreamer.py:694-707

@@ -503,6 +503,51 @@ def lambda_return(reward, boot, disc, lamb, term=None, cont_logit=None, last=Non
     return ret
 
 
+def lambda_return_bwd(d_ret, reward, value, cont_logit, disc, lamb, time_major=False):
+    """Backward of lambda_return's imagination case (boot = value, last = 0, term = 1 - sigmoid(cont_logit)).
+    d_ret (N, T - 1) row-major; reward / value / cont_logit: (N, T) views of any strides, the forward's.
+    -> (d_reward, d_value, d_cont_logit), each (N, T) row-major, or (T, N) with time_major (the rows of the imagined
+    heads' outputs); column t = 0 is zero."""
+    N, T = reward.shape
+    if tuple(d_ret.shape) != (N, T - 1) or tuple(value.shape) != (N, T) or tuple(cont_logit.shape) != (N, T):
+        raise ValueError(f"lambda_return_bwd shapes {tuple(d_ret.shape)} {tuple(reward.shape)} {tuple(value.shape)} "
+                         f"{tuple(cont_logit.shape)}")
+    _chk(d_ret, reward, value, cont_logit)
+    out = torch.empty((3, T, N) if time_major else (3, N, T), dtype=torch.float32, device=reward.device)
+    o_r, o_t = (1, N) if time_major else (T, 1)
+    nat.call("sd_lambda_return_bwd", p(_c(d_ret)), p(reward), reward.stride(0), reward.stride(1), p(cont_logit),
+             cont_logit.stride(0), cont_logit.stride(1), p(value), value.stride(0), value.stride(1), p(out[0]),
+             p(out[1]), p(out[2]), o_r, o_t, N, T, float(disc), float(lamb), stream())
+    return out[0], out[1], out[2]
+
+
+def twohot_mode_bwd(logits, bins, dout, dlogits=None):
+    """d twohot_mode / d logits times dout (one value per row): -> (rows, NB)"""
+    NB = logits.shape[-1]
+    rows = logits.numel() // NB
+    if dout.numel() != rows:
+        raise ValueError("twohot_mode_bwd: one upstream value per row")
+    _chk(logits, bins, dout)
+    dlogits = torch.empty_like(logits) if dlogits is None else dlogits
+    nat.call("sd_twohot_mode_bwd", p(_c(logits)), p(bins), p(_c(dout)), p(_c(dlogits)), rows, NB, stream())
+    return dlogits
+
+
+def bnormal_sample_bwd(d_action_norm, logits, action, min_std, max_std, seed, stream_id, step, row_offset, dx=None):
+    """d_action_norm (rows, A): gradient of action_norm(action); logits (rows, 2A) the actor's output, action (rows, A)
+    the sample sd_bnormal_sample drew with these counters -> the logits' gradient (rows, 2A)"""
+    rows, A = action.shape
+    if tuple(logits.shape) != (rows, 2 * A) or tuple(d_action_norm.shape) != (rows, A):
+        raise ValueError(f"bnormal_sample_bwd shapes {tuple(d_action_norm.shape)} {tuple(logits.shape)} "
+                         f"{tuple(action.shape)}")
+    _chk(d_action_norm, logits, action)
+    dx = torch.empty_like(logits) if dx is None else dx
+    sh, sp = seed_args(seed)
+    nat.call("sd_bnormal_sample_bwd", p(_c(d_action_norm)), p(_c(logits)), p(_c(action)), p(_c(dx)), rows, A,
+             float(min_std), float(max_std), sh, int(stream_id), int(step), int(row_offset), sp, stream())
+    return dx
+
+
 def return_ema(x, ema, offset_scale, quantiles=None, alpha=1e-2, q0=0.05, q1=0.95):
     x = _c(x)
     nat.call("sd_return_ema", p(x), x.numel(), p(ema), p(offset_scale), p(quantiles), float(alpha), float(q0),

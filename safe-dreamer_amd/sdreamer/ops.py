@@ -931,3 +931,164 @@ class InfoNCEFn(torch.autograd.Function):
         gg = g.reshape(1).contiguous()
         k.nat.call("sd_infonce_bwd", k.p(logits), nc, n, nc, ctx.off, k.p(lse), k.p(gg), 1.0 / n, k.p(dl), k.stream())
         return k.mm(dl, x2g, fast=True), None, None
+
+# ------------------------------------------------------------------------------------------------- imagined return
+def _mlp_recompute(mods, last, x, fast=False):
+    """Pre-activations of [Linear -> RMSNorm -> SiLU] x n + Linear on rows x: ([(pre, rstd)], logits). fast: split-bf16
+    contractions (contiguous rows only), else exact f32"""
+    saved = []
+    for lin, norm in mods:
+        pre = k.linear(x, lin.weight, lin.bias, fast=fast)
+        x, rstd = k.rmsnorm_fwd(pre, norm.weight)
+        saved.append((pre, rstd))
+    return saved, k.linear(x, last.weight, last.bias, fast=fast)
+
+
+def _mlp_input_grad(mods, last, saved, d_logits, rows=None, fast=False):
+    """d_logits back to the first layer's pre-norm output (the caller contracts it with the first weight into wherever
+    the input gradient goes). rows: (t, N): the saved activations are (H * N, U), this call's rows are step t's."""
+    d = k.mm(d_logits, last.weight, fast=fast)
+    for i in reversed(range(len(mods))):
+        pre, rstd = saved[i]
+        if rows is not None:
+            t, N = rows
+            pre, rstd = pre[t * N:(t + 1) * N], rstd[t * N:(t + 1) * N]
+        d = k.rmsnorm_bwd(pre, mods[i][1].weight, rstd, d)
+        if i:
+            d = k.mm(d, mods[i][0].weight, fast=fast)
+    return d
+
+
+IMAG_RETURN_MARKS = None  # measurement aid (tools/imag_return_bench.py): a list receives (tag, HIP event) per phase
+
+
+def _mark(tag):
+    if IMAG_RETURN_MARKS is not None:
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        IMAG_RETURN_MARKS.append((tag, ev))
+
+
+class ImagineReturnFn(torch.autograd.Function):
+    """ret0 (N,): the lambda-return of the frozen actor's imagined rollout from N start states (Dreamer._imagine_tm,
+    the reward / continue / value heads' modes, K.lambda_return with boot = value), differentiable in the start state
+    only. Forward: the no-grad path itself (fused imagination where the shape admits it, then _heads_returns as the
+    update calls it, slow critic included, so that ret is the update's bit for bit); it keeps feats (H1, N, F),
+    actions (H1, N, A) and the three (H1, N) head outputs. Backward: every pre-activation is recomputed from the saved
+    feats in (H * N)-row GEMMs (no sample is drawn again), the returns' and heads' backward runs on all rows at once,
+    and only the state gradient's walk t = H - 1 .. 0 through prior sample -> img_net -> GRU -> dyn_hid -> dyn_in ->
+    action sample -> actor is serial. The heads' contractions over all rows (recompute and backward) and the actor's
+    recompute run split-bf16, as the forward's heads do; the RSSM's recompute and every serial-step contraction are
+    exact f32. No parameter receives a gradient."""
+
+    @staticmethod
+    def forward(ctx, post_stoch, post_deter, agent, H1, seed, row_offset, keep):
+        r = agent.rssm
+        N = post_deter.shape[0]
+        if H1 < 2:
+            raise ValueError("the imagined return needs a horizon of at least one step (H1 >= 2)")
+        mlps = [agent.actor.mlp, agent.reward.mlp, agent.cont.mlp, agent.value.mlp]
+        if any(m._symlog_inputs or m.n < 1 for m in mlps):
+            raise NotImplementedError("imagined-return backward with symlog-input or layerless actor / heads")
+        s = post_stoch.detach().reshape(N, r.flat_stoch).contiguous()
+        h = post_deter.detach().contiguous()
+        feats, actions = agent._imagine_tm((s, h), H1, seed, row_offset)
+        rr = agent._heads_returns(feats)
+        if keep is not None:
+            keep.update(feats=feats, actions=actions, ret=rr["ret"])
+        ctx.save_for_backward(feats, actions, rr["i_rew"], rr["i_val"], rr["i_contl"])
+        ctx.agent, ctx.H1, ctx.seed, ctx.row_offset = agent, H1, seed, int(row_offset)
+        ctx.stoch_shape = post_stoch.shape
+        ctx.set_materialize_grads(False)
+        return rr["ret"][:, 0].clone()
+
+    @staticmethod
+    def backward(ctx, d_ret0):
+        if d_ret0 is None:
+            return (None,) * 7
+        from .rssm import STREAM_ACT, STREAM_IMG
+        feats, actions, i_rew, i_val, i_contl = ctx.saved_tensors
+        ag, H1, seed, ro = ctx.agent, ctx.H1, ctx.seed, ctx.row_offset
+        r = ag.rssm
+        P = r._p()
+        H, N, F = H1 - 1, feats.shape[1], feats.shape[2]
+        S, Kd, D, U, G, A = r._stoch, r._discrete, r._deter, r._hidden, r._blocks, ag.act_dim
+        SK, Dg, M = S * Kd, D // G, H * N
+        dev, f32 = feats.device, torch.float32
+        e = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)  # noqa: E731
+
+        # ---- batched over all rows: the returns' backward, then the heads' (rows of steps 1 .. H; step 0 has none)
+        _mark("begin")
+        d_ret = torch.zeros(N, H, dtype=f32, device=dev)
+        d_ret[:, 0] = d_ret0
+        d_rew, d_val, d_cl = k.lambda_return_bwd(d_ret, i_rew.t(), i_val.t(), i_contl.t(), 1 - 1 / ag.horizon, ag.lamb,
+                                                 time_major=True)
+        d_feat = e(H1, N, F)
+        d_feat[0].zero_()
+        xh = feats[1:].reshape(M, F)
+        dfh = d_feat[1:].view(M, F)
+        for i, (head, bins, d_out) in enumerate(((ag.reward, ag.rbins, d_rew), (ag.cont, None, d_cl),
+                                                 (ag.value, ag.vbins, d_val))):
+            saved, logits = _mlp_recompute(head.mlp._mods, head.last, xh, fast=True)
+            d_out = d_out[1:].reshape(M)
+            d_logits = d_out.view(M, 1) if bins is None else k.twohot_mode_bwd(logits, bins, d_out)
+            d0 = _mlp_input_grad(head.mlp._mods, head.last, saved, d_logits, fast=True)
+            k.gemm(d0, head.mlp._mods[0][0].weight, dfh, beta=1.0 if i else 0.0, fast=True)
+            del saved, logits
+        d_st, d_de = d_feat[..., :SK].contiguous(), d_feat[..., SK:].contiguous()
+        del d_feat, dfh
+        _mark("heads")
+
+        # ---- batched: every pre-activation of steps 0 .. H - 1 from the saved feats and actions
+        xa = feats[:H].reshape(M, F)
+        h_in = xa[:, SK:].contiguous()
+        a_n = k.action_norm(actions[:H].reshape(M, A))
+        xcat = e(M, 3 * U)
+        x0p, x1p, x2p = k.linear(h_in, P["W0"], P["b0"]), k.linear(xa[:, :SK], P["W1"], P["b1"]), \
+            k.linear(a_n, P["W2"], P["b2"])
+        _, r0 = k.rmsnorm_fwd(x0p, P["n0"], y=xcat[:, :U])
+        _, r1 = k.rmsnorm_fwd(x1p, P["n1"], y=xcat[:, U:2 * U])
+        _, r2 = k.rmsnorm_fwd(x2p, P["n2"], y=xcat[:, 2 * U:])
+        hp = k.mm(xcat, P["Wsh"].t(), bias=P["bh"])
+        k.gemm(h_in.view(M, G, Dg).permute(1, 0, 2), P["Wbd"].transpose(1, 2), hp.view(M, G, Dg).permute(1, 0, 2),
+               beta=1.0)
+        hh, rh = k.rmsnorm_fwd(hp, P["nh"])
+        gates = e(M, 3 * D)
+        k.gemm(hh.view(M, G, Dg).permute(1, 0, 2), P["Wg"].transpose(1, 2), gates.view(M, G, 3 * Dg).permute(1, 0, 2),
+               bias=P["bg"].view(G, 3 * Dg))
+        del xcat, hh
+        img_mods, img_last = r._img_mods()
+        img_saved, plogit = _mlp_recompute(img_mods, img_last, xh[:, SK:])
+        act_mods, act_last = ag.actor.mlp._mods, ag.actor.last
+        act_saved, alogit = _mlp_recompute(act_mods, act_last, xa, fast=True)
+        Wi0, Wa0 = img_mods[0][0].weight, act_mods[0][0].weight
+        dist = ag.config.actor.dist
+        step = lambda x, t: x[t * N:(t + 1) * N]  # noqa: E731
+        _mark("recompute")
+
+        # ---- serial: d_feat[t + 1] = (d_st[t + 1], d_de[t + 1]) is complete; add step t's part into d_feat[t]
+        for t in reversed(range(H)):
+            dl = k.onehot_sample_bwd(step(plogit, t), d_st[t + 1], Kd, r._unimix_ratio, seed, STREAM_IMG, t, ro * S)
+            k.gemm(_mlp_input_grad(img_mods, img_last, img_saved, dl, (t, N)), Wi0, d_de[t + 1], beta=1.0)
+            d_gates, _ = k.gru_bwd(step(gates, t), step(h_in, t), d_de[t + 1], G, dh=d_de[t], accumulate_dh=True)
+            d_hh = e(N, D)
+            k.gemm(d_gates.view(N, G, 3 * Dg).permute(1, 0, 2), P["Wg"], d_hh.view(N, G, Dg).permute(1, 0, 2))
+            d_hp = k.rmsnorm_bwd(step(hp, t), P["nh"], step(rh, t), d_hh)
+            d_xcat = k.mm(d_hp, P["Wsh"])
+            k.gemm(d_hp.view(N, G, Dg).permute(1, 0, 2), P["Wbd"], d_de[t].view(N, G, Dg).permute(1, 0, 2), beta=1.0)
+            d_x0p = k.rmsnorm_bwd(step(x0p, t), P["n0"], step(r0, t), d_xcat[:, :U])
+            k.gemm(d_x0p, P["W0"], d_de[t], beta=1.0)
+            d_x1p = k.rmsnorm_bwd(step(x1p, t), P["n1"], step(r1, t), d_xcat[:, U:2 * U])
+            k.gemm(d_x1p, P["W1"], d_st[t], beta=1.0)
+            d_x2p = k.rmsnorm_bwd(step(x2p, t), P["n2"], step(r2, t), d_xcat[:, 2 * U:])
+            d_an = k.mm(d_x2p, P["W2"])
+            if ag.act_discrete:  # the normalisation is the identity on a one-hot
+                d_al = k.onehot_sample_bwd(step(alogit, t), d_an, A, float(dist.unimix_ratio), seed, STREAM_ACT, t, ro)
+            else:
+                d_al = k.bnormal_sample_bwd(d_an, step(alogit, t), actions[t], float(dist.min_std),
+                                            float(dist.max_std), seed, STREAM_ACT, t, ro)
+            d_a0 = _mlp_input_grad(act_mods, act_last, act_saved, d_al, (t, N))
+            k.gemm(d_a0, Wa0[:, :SK], d_st[t], beta=1.0)
+            k.gemm(d_a0, Wa0[:, SK:], d_de[t], beta=1.0)
+            _mark("step")
+        return d_st[0].reshape(ctx.stoch_shape), d_de[0], None, None, None, None, None
