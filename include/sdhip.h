@@ -148,7 +148,8 @@ int sd_kl_bwd(const float* post, const float* prior, const float* kl_row, const 
               sd_stream stream);
 
 /* ---------------------------------------------------------------- heads
- * symexp two-hot (TwoHot, distributions.py:67-129; symexp_twohot bins 242-251): mode, log_prob fwd/bwd. NB odd <= 255 */
+ * symexp two-hot (TwoHot, distributions.py:67-129; symexp_twohot bins 242-251): mode, log_prob fwd/bwd. The mode pair:
+ * 1 <= NB <= 255, odd; the log_prob pair: 1 <= NB <= 256; anything else is SD_ESHAPE */
 int sd_twohot_mode(const float* logits, const float* bins, float* out, long rows, int NB, sd_stream stream);
 /* d mode / d logits: dlogits[r, j] = p[r, j] (bins[j] - mode[r]) dout[r]; mode summed as sd_twohot_mode sums it */
 int sd_twohot_mode_bwd(const float* logits, const float* bins, const float* dout, float* dlogits, long rows, int NB,
@@ -162,7 +163,7 @@ int sd_twohot_logp_bwd(const float* logits, const float* bins, const float* targ
  * slow / last (B, Tl); the Tr = Tl - 1 steps with a replay return ret (B, Tr) are the loss rows:
  * row_loss[b, t] = (1 - last[b, t]) * (-logp(ret[b, t]) - logp(slow[b, t])). The backward writes the gradient of
  * mean(row_loss) * gscale[0] (device scalar; inv_n = 1 / (B Tr)) for every (B, Tl) logits row (zero for t >= Tr).
- * NB <= 256. */
+ * 1 <= NB <= 256. */
 int sd_repval_loss_fwd(const float* logits, const float* bins, const float* ret, const float* slow, const float* last,
                        float* row_loss, int B, int Tl, int Tr, int NB, sd_stream s);
 int sd_repval_loss_bwd(const float* logits, const float* bins, const float* ret, const float* slow, const float* last,

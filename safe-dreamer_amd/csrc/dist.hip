@@ -692,7 +692,7 @@ extern "C" int sd_kl_bwd(const float* post, const float* prior, const float* kl_
 
 extern "C" int sd_twohot_mode(const float* logits, const float* bins, float* out, long rows, int NB, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (NB > 256 || NB % 2 == 0) return SD_ESHAPE;
+  if (NB < 1 || NB > 256 || NB % 2 == 0) return SD_ESHAPE;
   twohot_mode_kernel<<<blocks_for(rows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, out, rows, NB);
   SD_LAUNCH_CHECK();
   return SD_OK;
@@ -710,7 +710,7 @@ extern "C" int sd_twohot_mode_bwd(const float* logits, const float* bins, const 
 extern "C" int sd_twohot_logp_fwd(const float* logits, const float* bins, const float* target, float* logp, long rows,
                                   int NB, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (NB > 256) return SD_ESHAPE;
+  if (NB < 1 || NB > 256) return SD_ESHAPE;
   twohot_logp_fwd<<<blocks_for(rows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, target, logp, rows, NB);
   SD_LAUNCH_CHECK();
   return SD_OK;
@@ -719,7 +719,7 @@ extern "C" int sd_twohot_logp_fwd(const float* logits, const float* bins, const 
 extern "C" int sd_twohot_logp_bwd(const float* logits, const float* bins, const float* target, const float* glogp,
                                   float* dlogits, long rows, int NB, int accumulate, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (NB > 256) return SD_ESHAPE;
+  if (NB < 1 || NB > 256) return SD_ESHAPE;
   twohot_logp_bwd<<<blocks_for(rows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, target, glogp, dlogits, rows, NB,
                                                                     accumulate);
   SD_LAUNCH_CHECK();
@@ -729,7 +729,7 @@ extern "C" int sd_twohot_logp_bwd(const float* logits, const float* bins, const 
 extern "C" int sd_repval_loss_fwd(const float* logits, const float* bins, const float* ret, const float* slow,
                                   const float* last, float* row_loss, int B, int Tl, int Tr, int NB, sd_stream s) {
   if (B <= 0 || Tr <= 0) return SD_OK;
-  if (NB > 256 || Tr > Tl) return SD_ESHAPE;
+  if (NB < 1 || NB > 256 || Tr > Tl) return SD_ESHAPE;
   const long rows = (long)B * Tr;
   repval_fwd_kernel<<<blocks_for(rows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, ret, slow, last, row_loss, rows, Tl,
                                                                       Tr, NB);
@@ -741,7 +741,7 @@ extern "C" int sd_repval_loss_bwd(const float* logits, const float* bins, const 
                                   const float* last, const float* gscale, float inv_n, float* dlogits, int B, int Tl,
                                   int Tr, int NB, sd_stream s) {
   if (B <= 0) return SD_OK;
-  if (NB > 256 || !gscale || Tr > Tl) return SD_ESHAPE;
+  if (NB < 1 || NB > 256 || !gscale || Tr > Tl) return SD_ESHAPE;
   const long lrows = (long)B * Tl;
   repval_bwd_kernel<<<blocks_for(lrows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, ret, slow, last, gscale, inv_n,
                                                                        dlogits, lrows, Tl, Tr, NB);
@@ -754,7 +754,7 @@ extern "C" int sd_imag_ac_loss_fwd(const float* vl, const float* bins, const flo
                                    const float* ent, float coef, long N, int H, int H1, int NB, float* rows_v,
                                    float* rows_p, float* adv, sd_stream s) {
   if (N <= 0 || H <= 0) return SD_OK;
-  if (NB > 256 || H1 <= H) return SD_ESHAPE;
+  if (NB < 1 || NB > 256 || H1 <= H) return SD_ESHAPE;
   imag_ac_fwd_kernel<<<blocks_for(N * H, 4), 256, 0, (hipStream_t)s>>>(vl, bins, ret, slow, w, val, scale, logpi, ent,
                                                                        coef, N, H, H1, NB, rows_v, rows_p, adv);
   SD_LAUNCH_CHECK();
@@ -766,7 +766,7 @@ extern "C" int sd_imag_ac_loss_bwd(const float* vl, const float* bins, const flo
                                    float spolicy, float svalue, float coef, long N, int H, int H1, int NB, float* dvl,
                                    float* dlogpi, float* dent, sd_stream s) {
   if (N <= 0 || H <= 0) return SD_OK;
-  if (NB > 256 || H1 <= H) return SD_ESHAPE;
+  if (NB < 1 || NB > 256 || H1 <= H) return SD_ESHAPE;
   imag_ac_bwd_kernel<<<blocks_for(N * H, 4), 256, 0, (hipStream_t)s>>>(vl, bins, ret, slow, w, adv, gpolicy, gvalue,
                                                                        spolicy, svalue, coef, 1.f / (float)(N * H), N,
                                                                        H, H1, NB, dvl, dlogpi, dent);
@@ -777,7 +777,7 @@ extern "C" int sd_imag_ac_loss_bwd(const float* vl, const float* bins, const flo
 extern "C" int sd_bnormal_sample(const float* x, float* action, long rows, int A, float min_std, float max_std,
                                  uint64_t seed, int stream_id, int step, long row_offset, const uint64_t* seed_ptr,
                                  sd_stream s) {
-  if (rows <= 0) return SD_OK;
+  if (rows <= 0 || A <= 0) return SD_OK;
   bnormal_sample<<<blocks_for(rows * A, 256), 256, 0, (hipStream_t)s>>>(x, action, rows, A, min_std, max_std, seed,
                                                                         stream_id, step, row_offset, seed_ptr);
   SD_LAUNCH_CHECK();
@@ -796,7 +796,7 @@ extern "C" int sd_bnormal_sample_bwd(const float* d_action_norm, const float* x,
 
 extern "C" int sd_bnormal_logp_ent_fwd(const float* x, const float* action, float* logp, float* ent, long rows, int A,
                                        float min_std, float max_std, sd_stream s) {
-  if (rows <= 0) return SD_OK;
+  if (rows <= 0 || A <= 0) return SD_OK;
   bnormal_logp_ent_fwd<<<blocks_for(rows, 256), 256, 0, (hipStream_t)s>>>(x, action, logp, ent, rows, A, min_std,
                                                                           max_std);
   SD_LAUNCH_CHECK();
@@ -805,7 +805,7 @@ extern "C" int sd_bnormal_logp_ent_fwd(const float* x, const float* action, floa
 
 extern "C" int sd_bnormal_logp_ent_bwd(const float* x, const float* action, const float* glogp, const float* gent,
                                        float* dx, long rows, int A, float min_std, float max_std, sd_stream s) {
-  if (rows <= 0) return SD_OK;
+  if (rows <= 0 || A <= 0) return SD_OK;
   bnormal_logp_ent_bwd<<<blocks_for(rows * A, 256), 256, 0, (hipStream_t)s>>>(x, action, glogp, gent, dx, rows, A,
                                                                               min_std, max_std);
   SD_LAUNCH_CHECK();

@@ -366,7 +366,7 @@ extern "C" int sd_rmsnorm_fwd_ld(const float* x, const float* w, float* y, long 
                                  float eps, int act, sd_stream stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (M <= 0) return SD_OK;
-  if (N <= 0 || N > 4096) return SD_ESHAPE;
+  if (N <= 0 || N > 4096 || ldy < N) return SD_ESHAPE;
   const int team = team_for(N);
   if (vec_ok(N, x, w, y, ldy)) {
     const int grid = grid_for<64>(M);

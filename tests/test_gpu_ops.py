@@ -2,6 +2,12 @@
 
 Tolerances: fp32 kernels with different summation order — max abs error scaled to the data (stated per test);
 discrete outputs (latent indices) bit-exact except where the top-2 gumbel margin is below 1e-5.
+
+The row kernels (RMSNorm + SiLU, column sums, sampler and actor heads, KL, two-hot family, Bernoulli, GRU gates,
+λ-return, ReturnEMA) are pinned to float64, elementwise and at every arm of their dispatch, by
+tests/test_gpu_rowops_f64.py (cases and references: tests/rowop_models.py, checked on the CPU by
+tests/test_rowop_parity_cpu.py). The tests below keep their one or few shapes and their tolerances,
+which that file uses as caps.
 """
 import numpy as np
 import pytest
