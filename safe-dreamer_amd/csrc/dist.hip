@@ -9,6 +9,15 @@
 //  * bounded normal (distributions.py:217-222): sample, log_prob, entropy fwd/bwd; discrete-actor log_prob/entropy;
 //  * Bernoulli continue head (torchd.Bernoulli(logits)): log_prob fwd/bwd;
 //  * Deter gates (rssm.py:65-75): r = sigmoid, c = tanh(r*c), u = sigmoid(u-1), h' = u*c + (1-u)*h, fwd/bwd.
+//
+// Each family states its device math once and its kernels are that math plus their loads and stores: OneHot (a team's
+// unimix categorical) for the one-hot heads, WaveRow / row_softmax64 / TwoHot / twohot_mode / ValuePair for the two-hot
+// ones, bnormal_loc_scale for the bounded normal. The two KL kernels each spell out their double softmax: any shared
+// function that also gives the backward's pb makes hipcc lay out kl_fwd's loop otherwise (2 VGPRs and 2 SGPRs fewer,
+// three instructions fewer), and one that does not is of no use to the backward. The host side is launch, with_team and
+// the two-hot shape predicate; every entry point is its early return, its guard and one launch.
+#include <type_traits>
+
 #include "common.h"
 #include "philox.h"
 #include "sdhip.h"
@@ -16,32 +25,54 @@
 
 namespace {
 
+// ---------------------------------------------------------------- one-hot heads (one team of T lanes per categorical)
+// Lane lt of team g holds logit lt of categorical g (lanes >= K idle): p = softmax(l), pp its unimix, nl the normalised
+// unimix logits. The teams with g past the last categorical exit before load(); whole teams exit together.
+template <int T>
+struct OneHot {
+  const int lt = threadIdx.x % T;
+  const long g = ((long)blockIdx.x * blockDim.x + threadIdx.x) / T;
+  bool act;         // act, p, pp, nl: set by load(), which every kernel calls right after its exit test
+  float p, pp, nl;
+  SD_DEV void load(const float* logits, int K, float unimix) {
+    act = lt < K;
+    const float l = act ? logits[g * K + lt] : 0.f;
+    unimix_forward<T>(l, act, K, unimix, p, pp, nl);
+  }
+  // the straight-through sample's soft values and index, the Gumbel noise drawn from the categorical's Philox counters
+  SD_DEV void sample(int K, uint64_t seed, uint32_t stream, uint32_t step, long group_offset, float& ys,
+                     int& idx) const {
+    const float gn = act ? sd_gumbel(seed, stream, step, (uint64_t)(g + group_offset) * K + lt) : 0.f;
+    st_soft<T>(nl, gn, act, ys, idx, lt);
+  }
+  // argmax of the action one-hot (value.max(-1)[1]: first max)
+  SD_DEV int chosen(const float* action, int K) const {
+    return team_first_max<T>(act ? action[g * K + lt] : -INFINITY, act ? lt : 0x7fffffff);
+  }
+  SD_DEV float backward(float dnl, float unimix) const { return unimix_backward<T>(dnl, p, pp, nl, act, unimix); }
+};
+
 template <int T>
 __global__ void onehot_sample_fwd(const float* __restrict__ logits, float* __restrict__ out, int* __restrict__ index,
                                   float* __restrict__ entropy, long groups, int K, float unimix, uint64_t seed,
                                   uint32_t stream, uint32_t step, long group_offset, const uint64_t* seed_ptr) {
   if (seed_ptr) seed += *seed_ptr;
-  const int lt = threadIdx.x % T;
-  const long g = ((long)blockIdx.x * blockDim.x + threadIdx.x) / T;
-  if (g >= groups) return;  // whole teams exit together (groups are team-aligned)
-  const bool act = lt < K;
-  const float l = act ? logits[g * K + lt] : 0.f;
-  float p, pp, nl;
-  unimix_forward<T>(l, act, K, unimix, p, pp, nl);
+  OneHot<T> c;
+  if (c.g >= groups) return;
+  c.load(logits, K, unimix);
   if (entropy) {
-    const float h = group_sum<T>(act ? -expf(nl) * nl : 0.f);
-    if (lt == 0) entropy[g] = h;
+    const float h = group_sum<T>(c.act ? -expf(c.nl) * c.nl : 0.f);
+    if (c.lt == 0) entropy[c.g] = h;
   }
   if (!out) return;
-  const float gn = act ? sd_gumbel(seed, stream, step, (uint64_t)(g + group_offset) * K + lt) : 0.f;
   float ys;
   int idx;
-  st_soft<T>(nl, gn, act, ys, idx, lt);
-  if (act) {
-    const float hard = lt == idx ? 1.f : 0.f;
-    out[g * K + lt] = (hard - ys) + ys;
+  c.sample(K, seed, stream, step, group_offset, ys, idx);
+  if (c.act) {
+    const float hard = c.lt == idx ? 1.f : 0.f;
+    out[c.g * K + c.lt] = (hard - ys) + ys;
   }
-  if (index && lt == 0) index[g] = idx;
+  if (index && c.lt == 0) index[c.g] = idx;
 }
 
 template <int T>
@@ -50,75 +81,46 @@ __global__ void onehot_sample_bwd(const float* __restrict__ logits, const float*
                                   uint32_t stream, uint32_t step, long group_offset, int accumulate,
                                   const uint64_t* seed_ptr) {
   if (seed_ptr) seed += *seed_ptr;
-  const int lt = threadIdx.x % T;
-  const long g = ((long)blockIdx.x * blockDim.x + threadIdx.x) / T;
-  if (g >= groups) return;
-  const bool act = lt < K;
-  const float l = act ? logits[g * K + lt] : 0.f;
-  float p, pp, nl;
-  unimix_forward<T>(l, act, K, unimix, p, pp, nl);
-  const float gn = act ? sd_gumbel(seed, stream, step, (uint64_t)(g + group_offset) * K + lt) : 0.f;
+  OneHot<T> c;
+  if (c.g >= groups) return;
+  c.load(logits, K, unimix);
   float ys;
   int idx;
-  st_soft<T>(nl, gn, act, ys, idx, lt);
-  const float d = act ? dout[g * K + lt] : 0.f;
+  c.sample(K, seed, stream, step, group_offset, ys, idx);
+  const float d = c.act ? dout[c.g * K + c.lt] : 0.f;
   const float sd = group_sum<T>(d * ys);
-  const float dnl = act ? ys * (d - sd) : 0.f;
-  const float dl = unimix_backward<T>(dnl, p, pp, nl, act, unimix);
-  if (act) dlogits[g * K + lt] = accumulate ? dlogits[g * K + lt] + dl : dl;
+  const float dl = c.backward(c.act ? ys * (d - sd) : 0.f, unimix);
+  if (c.act) dlogits[c.g * K + c.lt] = accumulate ? dlogits[c.g * K + c.lt] + dl : dl;
 }
 
 // discrete actor: logp(a) = nl[argmax a], entropy = -sum exp(nl) nl  (OneHotCategorical.log_prob / entropy)
 template <int T>
 __global__ void onehot_logp_ent_fwd(const float* __restrict__ logits, const float* __restrict__ action,
                                     float* __restrict__ logp, float* __restrict__ ent, long rows, int K, float unimix) {
-  const int lt = threadIdx.x % T;
-  const long g = ((long)blockIdx.x * blockDim.x + threadIdx.x) / T;
-  if (g >= rows) return;
-  const bool act = lt < K;
-  const float l = act ? logits[g * K + lt] : 0.f;
-  float p, pp, nl;
-  unimix_forward<T>(l, act, K, unimix, p, pp, nl);
-  // argmax of the action one-hot (value.max(-1)[1]: first max)
-  float best = act ? action[g * K + lt] : -INFINITY;
-  int bi = act ? lt : 0x7fffffff;
-#pragma unroll
-  for (int o = T / 2; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
-  const float sel = group_sum<T>(lt == bi ? nl : 0.f);
-  const float h = group_sum<T>(act ? -expf(nl) * nl : 0.f);
-  if (lt == 0) { logp[g] = sel; ent[g] = h; }
+  OneHot<T> c;
+  if (c.g >= rows) return;
+  c.load(logits, K, unimix);
+  const int bi = c.chosen(action, K);
+  const float sel = group_sum<T>(c.lt == bi ? c.nl : 0.f);
+  const float h = group_sum<T>(c.act ? -expf(c.nl) * c.nl : 0.f);
+  if (c.lt == 0) { logp[c.g] = sel; ent[c.g] = h; }
 }
 
 template <int T>
 __global__ void onehot_logp_ent_bwd(const float* __restrict__ logits, const float* __restrict__ action,
                                     const float* __restrict__ glogp, const float* __restrict__ gent,
                                     float* __restrict__ dlogits, long rows, int K, float unimix) {
-  const int lt = threadIdx.x % T;
-  const long g = ((long)blockIdx.x * blockDim.x + threadIdx.x) / T;
-  if (g >= rows) return;
-  const bool act = lt < K;
-  const float l = act ? logits[g * K + lt] : 0.f;
-  float p, pp, nl;
-  unimix_forward<T>(l, act, K, unimix, p, pp, nl);
-  float best = act ? action[g * K + lt] : -INFINITY;
-  int bi = act ? lt : 0x7fffffff;
-#pragma unroll
-  for (int o = T / 2; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
-  const float s = act ? expf(nl) : 0.f;
-  const float h = group_sum<T>(act ? -s * nl : 0.f);
-  const float gl = glogp ? glogp[g] : 0.f, ge = gent ? gent[g] : 0.f;
+  OneHot<T> c;
+  if (c.g >= rows) return;
+  c.load(logits, K, unimix);
+  const int bi = c.chosen(action, K);
+  const float s = c.act ? expf(c.nl) : 0.f;
+  const float h = group_sum<T>(c.act ? -s * c.nl : 0.f);
+  const float gl = glogp ? glogp[c.g] : 0.f, ge = gent ? gent[c.g] : 0.f;
   // d logp / d nl = onehot(bi);  d H / d nl_k = -s_k (1 + nl_k + H)   (probs = softmax(nl))
-  const float dnl = act ? (lt == bi ? gl : 0.f) + ge * (-s * (1.f + nl + h)) : 0.f;
-  const float dl = unimix_backward<T>(dnl, p, pp, nl, act, unimix);
-  if (act) dlogits[g * K + lt] = dl;
+  const float dnl = c.act ? (c.lt == bi ? gl : 0.f) + ge * (-s * (1.f + c.nl + h)) : 0.f;
+  const float dl = c.backward(dnl, unimix);
+  if (c.act) dlogits[c.g * K + c.lt] = dl;
 }
 
 // ---------------------------------------------------------------- KL (raw logits) summed over S, per row
@@ -185,6 +187,12 @@ __global__ void kl_bwd(const float* __restrict__ post, const float* __restrict__
 }
 
 // ---------------------------------------------------------------- symexp two-hot (one wave per row)
+// wave `wave` of a 256-thread block works on row r = 4 * block + wave; the waves with r >= rows exit at once
+struct WaveRow {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + wave;
+};
+
 SD_DEV void row_softmax64(const float* l, int NB, float (&p)[4], float& lse, int lane) {
   float v[4];
   float m = -INFINITY;
@@ -208,62 +216,75 @@ SD_DEV void row_softmax64(const float* l, int NB, float (&p)[4], float& lse, int
   lse = m + logf(s);
 }
 
-// mode = p[c] b[c] + sum_i (p[c-1-i] b[c-1-i] + p[c+1+i] b[c+1+i]),  c = (NB-1)/2  (NB odd)
+// mode = p[c] b[c] + sum_i (p[c-1-i] b[c-1-i] + p[c+1+i] b[c+1+i]),  c = (NB-1)/2  (NB odd): twohot_mode stages the
+// row's p in sp (the wave's 256 floats of LDS) and sums the +- pairs on every lane; value() adds the centre bin. The
+// forward (lane 0) and the backward (every lane) both take the mode from here, so they hold the same value.
+struct TwoHotMode {
+  int c;
+  float acc;
+  SD_DEV float value(const float* sp, const float* bins) const { return sp[c] * bins[c] + acc; }
+};
+SD_DEV TwoHotMode twohot_mode(float* sp, const float (&p)[4], const float* bins, int NB, int lane) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) sp[lane + 64 * j] = p[j];
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  const int c = (NB - 1) / 2;
+  float acc = 0.f;
+  for (int i = lane; i < c; i += 64) {
+    const float lo = sp[c - 1 - i] * bins[c - 1 - i];
+    const float hi = sp[c + 1 + i] * bins[c + 1 + i];
+    acc += lo + hi;
+  }
+  return {c, wave_sum(acc)};
+}
+
 __global__ void twohot_mode_kernel(const float* __restrict__ logits, const float* __restrict__ bins,
                                    float* __restrict__ out, long rows, int NB) {
   __shared__ float sp[4][256];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + wave;
-  if (r >= rows) return;
+  const WaveRow w;
+  if (w.r >= rows) return;
   float p[4], lse;
-  row_softmax64(logits + r * NB, NB, p, lse, lane);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) sp[wave][lane + 64 * j] = p[j];
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  const int c = (NB - 1) / 2;
-  float acc = 0.f;
-  for (int i = lane; i < c; i += 64) {
-    const float lo = sp[wave][c - 1 - i] * bins[c - 1 - i];
-    const float hi = sp[wave][c + 1 + i] * bins[c + 1 + i];
-    acc += lo + hi;
-  }
-  acc = wave_sum(acc);
-  if (lane == 0) out[r] = sp[wave][c] * bins[c] + acc;
+  row_softmax64(logits + w.r * NB, NB, p, lse, w.lane);
+  const TwoHotMode m = twohot_mode(sp[w.wave], p, bins, NB, w.lane);
+  if (w.lane == 0) out[w.r] = m.value(sp[w.wave], bins);
 }
 
-// d mode / d logits[j] = p[j] (bins[j] - mode), times the row's upstream gradient; mode summed in twohot_mode_kernel's
-// order (the +- bin pairs), so both kernels hold the same value
+// d mode / d logits[j] = p[j] (bins[j] - mode), times the row's upstream gradient
 __global__ void twohot_mode_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ bins,
                                        const float* __restrict__ dout, float* __restrict__ dlogits, long rows, int NB) {
   __shared__ float sp[4][256];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + wave;
-  if (r >= rows) return;
+  const WaveRow w;
+  if (w.r >= rows) return;
   float p[4], lse;
-  row_softmax64(logits + r * NB, NB, p, lse, lane);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) sp[wave][lane + 64 * j] = p[j];
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  const int c = (NB - 1) / 2;
-  float acc = 0.f;
-  for (int i = lane; i < c; i += 64) {
-    const float lo = sp[wave][c - 1 - i] * bins[c - 1 - i];
-    const float hi = sp[wave][c + 1 + i] * bins[c + 1 + i];
-    acc += lo + hi;
-  }
-  acc = wave_sum(acc);
-  const float mode = sp[wave][c] * bins[c] + acc;
-  const float d = dout[r];
+  row_softmax64(logits + w.r * NB, NB, p, lse, w.lane);
+  const float mode = twohot_mode(sp[w.wave], p, bins, NB, w.lane).value(sp[w.wave], bins);
+  const float d = dout[w.r];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int col = lane + 64 * j;
-    if (col < NB) dlogits[r * NB + col] = p[j] * (bins[col] - mode) * d;
+    const int col = w.lane + 64 * j;
+    if (col < NB) dlogits[w.r * NB + col] = p[j] * (bins[col] - mode) * d;
   }
 }
 
-SD_DEV void twohot_target(const float* bins, int NB, float t, int& below, int& above, float& wb, float& wa, int lane) {
+// The two-hot encoding of a target: weight wb on bin `below`, wa on bin `above`.
+struct TwoHot {
+  int below, above;
+  float wb, wa;
+  // log_prob of the target under logits l with log-sum-exp lse
+  SD_DEV float logp(const float* l, float lse) const {
+    float v = wb * (l[below] - lse);
+    v += wa * (l[above] - lse);
+    return v;
+  }
+  // d logp / d l[c], p = softmax(l)[c]
+  SD_DEV float grad(int c, float p) const {
+    const float td = (c == below ? wb : 0.f) + (c == above ? wa : 0.f);
+    return td - p * (wb + wa);
+  }
+};
+
+SD_DEV TwoHot twohot_target(const float* bins, int NB, float t, int lane) {
   // below = #(bins <= t) - 1, above = NB - #(bins > t), clamped (distributions.py:106-109)
   int cle = 0, cgt = 0;
   for (int c = lane; c < NB; c += 64) {
@@ -276,63 +297,70 @@ SD_DEV void twohot_target(const float* bins, int NB, float t, int& below, int& a
     cle += __shfl_xor(cle, o, 64);
     cgt += __shfl_xor(cgt, o, 64);
   }
-  below = min(max(cle - 1, 0), NB - 1);
-  above = min(max(NB - cgt, 0), NB - 1);
-  const bool eq = below == above;
-  const float db = eq ? 1.f : fabsf(bins[below] - t);
-  const float da = eq ? 1.f : fabsf(bins[above] - t);
+  TwoHot h;
+  h.below = min(max(cle - 1, 0), NB - 1);
+  h.above = min(max(NB - cgt, 0), NB - 1);
+  const bool eq = h.below == h.above;
+  const float db = eq ? 1.f : fabsf(bins[h.below] - t);
+  const float da = eq ? 1.f : fabsf(bins[h.above] - t);
   const float tot = db + da;
-  wb = da / tot;
-  wa = db / tot;
+  h.wb = da / tot;
+  h.wa = db / tot;
+  return h;
 }
 
 __global__ void twohot_logp_fwd(const float* __restrict__ logits, const float* __restrict__ bins,
                                 const float* __restrict__ target, float* __restrict__ logp, long rows, int NB) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + wave;
-  if (r >= rows) return;
-  const float* l = logits + r * NB;
+  const WaveRow w;
+  if (w.r >= rows) return;
+  const float* l = logits + w.r * NB;
   float p[4], lse;
-  row_softmax64(l, NB, p, lse, lane);
-  int below, above;
-  float wb, wa;
-  twohot_target(bins, NB, target[r], below, above, wb, wa, lane);
-  if (lane == 0) {
-    float v = wb * (l[below] - lse);
-    v += wa * (l[above] - lse);
-    logp[r] = v;
-  }
+  row_softmax64(l, NB, p, lse, w.lane);
+  const TwoHot h = twohot_target(bins, NB, target[w.r], w.lane);
+  if (w.lane == 0) logp[w.r] = h.logp(l, lse);
 }
 
 __global__ void twohot_logp_bwd(const float* __restrict__ logits, const float* __restrict__ bins,
                                 const float* __restrict__ target, const float* __restrict__ glogp,
                                 float* __restrict__ dlogits, long rows, int NB, int accumulate) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + wave;
-  if (r >= rows) return;
-  const float* l = logits + r * NB;
+  const WaveRow w;
+  if (w.r >= rows) return;
   float p[4], lse;
-  row_softmax64(l, NB, p, lse, lane);
-  int below, above;
-  float wb, wa;
-  twohot_target(bins, NB, target[r], below, above, wb, wa, lane);
-  const float gsc = glogp[r];
-  const float tsum = wb + wa;
+  row_softmax64(logits + w.r * NB, NB, p, lse, w.lane);
+  const TwoHot h = twohot_target(bins, NB, target[w.r], w.lane);
+  const float gsc = glogp[w.r];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int c = lane + 64 * j;
+    const int c = w.lane + 64 * j;
     if (c < NB) {
-      const float td = (c == below ? wb : 0.f) + (c == above ? wa : 0.f);
-      const float v = gsc * (td - p[j] * tsum);
-      float* d = dlogits + r * NB + c;
+      const float v = gsc * h.grad(c, p[j]);
+      float* d = dlogits + w.r * NB + c;
       *d = accumulate ? *d + v : v;
     }
   }
 }
 
+// The value-loss term of one row: two targets (the return and the slow critic's value) under one softmax of the value
+// head's logits l. Forward -logp(ret) - logp(slow), in two steps so that a kernel reads the four logits first and
+// negates where it weights the term (the order its loads and arithmetic always had); backward, for the row's
+// d loss / d term g, the sum of the two log-prob gradients in one pass:
+// g (td_ret - p tsum_ret) + g (td_slow - p tsum_slow).
+struct ValuePair {
+  TwoHot ret, slow;
+  struct LogP {
+    float lr, ls;
+    SD_DEV float loss() const { return -lr - ls; }
+  };
+  SD_DEV LogP logp(const float* l, float lse) const {
+    const float lr = ret.logp(l, lse);
+    const float ls = slow.logp(l, lse);
+    return {lr, ls};
+  }
+  SD_DEV float grad(float g, int c, float p) const { return g * ret.grad(c, p) + g * slow.grad(c, p); }
+};
+
 // Replay-value loss (dreamer.py:652-658): row r's term w[r] * (-logp(ret[r]) - logp(slow[r])) under the TwoHot head
-// logits (distributions.py:100-129), and its logits gradient for a given d loss / d term (one wave per row). The
-// backward is the sum of the two twohot_logp_bwd terms in one pass: g (td_ret + td_slow - p (tsum_ret + tsum_slow)),
+// logits (distributions.py:100-129), and its logits gradient for a given d loss / d term (one wave per row), with
 // g = -w[r] * gscale[0] * inv_n (gscale: device scalar, d total / d mean).
 // replay-value rows (dreamer.py:638-658): loss row r = (b, t < Tr) reads logits / slow / last row b * Tl + t (the value
 // head ran on all Tl posterior steps; Tr = Tl - 1 of them have a return) and ret[r]; weight = 1 - last.
@@ -340,23 +368,16 @@ __global__ void repval_fwd_kernel(const float* __restrict__ logits, const float*
                                   const float* __restrict__ ret, const float* __restrict__ slow,
                                   const float* __restrict__ last, float* __restrict__ row_loss, long rows, int Tl,
                                   int Tr, int NB) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + wave;
-  if (r >= rows) return;
-  const long lr_ = (r / Tr) * Tl + r % Tr;
+  const WaveRow w;
+  if (w.r >= rows) return;
+  const long lr_ = (w.r / Tr) * Tl + w.r % Tr;
   const float* l = logits + lr_ * NB;
   float p[4], lse;
-  row_softmax64(l, NB, p, lse, lane);
-  int b1, a1, b2, a2;
-  float wb1, wa1, wb2, wa2;
-  twohot_target(bins, NB, ret[r], b1, a1, wb1, wa1, lane);
-  twohot_target(bins, NB, slow[lr_], b2, a2, wb2, wa2, lane);
-  if (lane == 0) {
-    float lr = wb1 * (l[b1] - lse);
-    lr += wa1 * (l[a1] - lse);
-    float ls = wb2 * (l[b2] - lse);
-    ls += wa2 * (l[a2] - lse);
-    row_loss[r] = (1.f - last[lr_]) * (-lr - ls);
+  row_softmax64(l, NB, p, lse, w.lane);
+  const ValuePair v{twohot_target(bins, NB, ret[w.r], w.lane), twohot_target(bins, NB, slow[lr_], w.lane)};
+  if (w.lane == 0) {
+    const ValuePair::LogP lp = v.logp(l, lse);
+    row_loss[w.r] = (1.f - last[lr_]) * lp.loss();
   }
 }
 
@@ -365,34 +386,25 @@ __global__ void repval_bwd_kernel(const float* __restrict__ logits, const float*
                                   const float* __restrict__ ret, const float* __restrict__ slow,
                                   const float* __restrict__ last, const float* __restrict__ gscale, float inv_n,
                                   float* __restrict__ dlogits, long lrows, int Tl, int Tr, int NB) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long lr_ = (long)blockIdx.x * 4 + wave;
+  const WaveRow w;
+  const long lr_ = w.r;
   if (lr_ >= lrows) return;
   const int t = (int)(lr_ % Tl);
   if (t >= Tr) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (lane + 64 * j < NB) dlogits[lr_ * NB + lane + 64 * j] = 0.f;
+      if (w.lane + 64 * j < NB) dlogits[lr_ * NB + w.lane + 64 * j] = 0.f;
     return;
   }
   const long r = (lr_ / Tl) * Tr + t;
-  const float* l = logits + lr_ * NB;
   float p[4], lse;
-  row_softmax64(l, NB, p, lse, lane);
-  int b1, a1, b2, a2;
-  float wb1, wa1, wb2, wa2;
-  twohot_target(bins, NB, ret[r], b1, a1, wb1, wa1, lane);
-  twohot_target(bins, NB, slow[lr_], b2, a2, wb2, wa2, lane);
+  row_softmax64(logits + lr_ * NB, NB, p, lse, w.lane);
+  const ValuePair v{twohot_target(bins, NB, ret[r], w.lane), twohot_target(bins, NB, slow[lr_], w.lane)};
   const float g = -(1.f - last[lr_]) * (gscale[0] * inv_n);
-  const float t1 = wb1 + wa1, t2 = wb2 + wa2;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int c = lane + 64 * j;
-    if (c < NB) {
-      const float td1 = (c == b1 ? wb1 : 0.f) + (c == a1 ? wa1 : 0.f);
-      const float td2 = (c == b2 ? wb2 : 0.f) + (c == a2 ? wa2 : 0.f);
-      dlogits[lr_ * NB + c] = g * (td1 - p[j] * t1) + g * (td2 - p[j] * t2);
-    }
+    const int c = w.lane + 64 * j;
+    if (c < NB) dlogits[lr_ * NB + c] = v.grad(g, c, p[j]);
   }
 }
 
@@ -406,27 +418,21 @@ __global__ void imag_ac_fwd_kernel(const float* __restrict__ vl, const float* __
                                    const float* __restrict__ scale, const float* __restrict__ logpi,
                                    const float* __restrict__ ent, float coef, long N, int H, int H1, int NB,
                                    float* __restrict__ rows_v, float* __restrict__ rows_p, float* __restrict__ adv) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + wave;
+  const WaveRow wr;
+  const long r = wr.r;
   if (r >= N * H) return;
   const long n = r % N;
   const int t = (int)(r / N);
   const float* l = vl + r * NB;
   const float rt = ret[n * H + t];
   float p[4], lse;
-  row_softmax64(l, NB, p, lse, lane);
-  int b1, a1, b2, a2;
-  float wb1, wa1, wb2, wa2;
-  twohot_target(bins, NB, rt, b1, a1, wb1, wa1, lane);
-  twohot_target(bins, NB, slow[r], b2, a2, wb2, wa2, lane);
-  if (lane == 0) {
-    float lr = wb1 * (l[b1] - lse);
-    lr += wa1 * (l[a1] - lse);
-    float ls = wb2 * (l[b2] - lse);
-    ls += wa2 * (l[a2] - lse);
+  row_softmax64(l, NB, p, lse, wr.lane);
+  const ValuePair v{twohot_target(bins, NB, rt, wr.lane), twohot_target(bins, NB, slow[r], wr.lane)};
+  if (wr.lane == 0) {
+    const ValuePair::LogP lp = v.logp(l, lse);
     const float wt = w[n * H1 + t];
     const float a = (rt - val[(long)t * N + n]) / scale[0];
-    rows_v[r] = wt * (-lr - ls);
+    rows_v[r] = wt * lp.loss();
     rows_p[r] = wt * -(logpi[r] * a + coef * ent[r]);
     adv[n * H + t] = a;
   }
@@ -438,31 +444,22 @@ __global__ void imag_ac_bwd_kernel(const float* __restrict__ vl, const float* __
                                    const float* __restrict__ gp, const float* __restrict__ gv, float sp, float sv,
                                    float coef, float inv_n, long N, int H, int H1, int NB, float* __restrict__ dvl,
                                    float* __restrict__ dlogpi, float* __restrict__ dent) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + wave;
+  const WaveRow wr;
+  const long r = wr.r;
   if (r >= N * H) return;
   const long n = r % N;
   const int t = (int)(r / N);
-  const float* l = vl + r * NB;
   float p[4], lse;
-  row_softmax64(l, NB, p, lse, lane);
-  int b1, a1, b2, a2;
-  float wb1, wa1, wb2, wa2;
-  twohot_target(bins, NB, ret[n * H + t], b1, a1, wb1, wa1, lane);
-  twohot_target(bins, NB, slow[r], b2, a2, wb2, wa2, lane);
+  row_softmax64(vl + r * NB, NB, p, lse, wr.lane);
+  const ValuePair v{twohot_target(bins, NB, ret[n * H + t], wr.lane), twohot_target(bins, NB, slow[r], wr.lane)};
   const float wt = w[n * H1 + t];
   const float g = -wt * ((gv ? gv[0] * sv : 0.f) * inv_n);
-  const float t1 = wb1 + wa1, t2 = wb2 + wa2;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int c = lane + 64 * j;
-    if (c < NB) {
-      const float td1 = (c == b1 ? wb1 : 0.f) + (c == a1 ? wa1 : 0.f);
-      const float td2 = (c == b2 ? wb2 : 0.f) + (c == a2 ? wa2 : 0.f);
-      dvl[r * NB + c] = g * (td1 - p[j] * t1) + g * (td2 - p[j] * t2);
-    }
+    const int c = wr.lane + 64 * j;
+    if (c < NB) dvl[r * NB + c] = v.grad(g, c, p[j]);
   }
-  if (lane == 0) {
+  if (wr.lane == 0) {
     const float gg = -wt * ((gp ? gp[0] * sp : 0.f) * inv_n);
     dlogpi[r] = gg * adv[n * H + t];
     dent[r] = gg * coef;
@@ -470,6 +467,19 @@ __global__ void imag_ac_bwd_kernel(const float* __restrict__ vl, const float* __
 }
 
 // ---------------------------------------------------------------- bounded normal actor
+// row r, action dim j of the head output x (rows, 2 A): loc = tanh(x[r, j]), sg = sigmoid(x[r, A + j] + 2) and
+// scale() = (max_std - min_std) sg + min_std
+struct BNormal {
+  float loc, sg;
+  SD_DEV float scale(float min_std, float max_std) const { return (max_std - min_std) * sg + min_std; }
+};
+SD_DEV BNormal bnormal_loc_scale(const float* x, long im, long is) {
+  BNormal b;
+  b.loc = tanhf(x[im]);
+  b.sg = sigmoidf_(x[is] + 2.f);
+  return b;
+}
+
 __global__ void bnormal_sample(const float* __restrict__ x, float* __restrict__ action, long rows, int A, float min_std,
                                float max_std, uint64_t seed, uint32_t stream, uint32_t step, long row_offset,
                                const uint64_t* seed_ptr) {
@@ -478,10 +488,10 @@ __global__ void bnormal_sample(const float* __restrict__ x, float* __restrict__ 
   if (t >= rows * A) return;
   const long r = t / A;
   const int j = (int)(t % A);
-  const float loc = tanhf(x[r * 2 * A + j]);
-  const float sc = (max_std - min_std) * sigmoidf_(x[r * 2 * A + A + j] + 2.f) + min_std;
+  const BNormal b = bnormal_loc_scale(x, r * 2 * A + j, r * 2 * A + A + j);
+  const float sc = b.scale(min_std, max_std);
   const float eps = sd_normal(seed, stream, step, (uint64_t)(r + row_offset) * A + j);
-  action[t] = loc + eps * sc;
+  action[t] = b.loc + eps * sc;
 }
 
 // Reparameterised gradient of the sampled, normalised action a / max(|a|, 1) (the divisor a constant, rssm.py:44):
@@ -495,12 +505,11 @@ __global__ void bnormal_sample_bwd(const float* __restrict__ d_an, const float* 
   if (t >= rows * A) return;
   const long r = t / A;
   const int j = (int)(t % A);
-  const float loc = tanhf(x[r * 2 * A + j]);
-  const float sg = sigmoidf_(x[r * 2 * A + A + j] + 2.f);
+  const BNormal b = bnormal_loc_scale(x, r * 2 * A + j, r * 2 * A + A + j);
   const float eps = sd_normal(seed, stream, step, (uint64_t)(r + row_offset) * A + j);
   const float da = d_an[t] / fmaxf(fabsf(action[t]), 1.f);
-  dx[r * 2 * A + j] = da * (1.f - loc * loc);
-  dx[r * 2 * A + A + j] = da * eps * (max_std - min_std) * sg * (1.f - sg);
+  dx[r * 2 * A + j] = da * (1.f - b.loc * b.loc);
+  dx[r * 2 * A + A + j] = da * eps * (max_std - min_std) * b.sg * (1.f - b.sg);
 }
 
 __global__ void bnormal_logp_ent_fwd(const float* __restrict__ x, const float* __restrict__ action,
@@ -511,9 +520,9 @@ __global__ void bnormal_logp_ent_fwd(const float* __restrict__ x, const float* _
   const float c0 = 0.91893853320467274178f;  // log(sqrt(2*pi))
   float lp = 0.f, h = 0.f;
   for (int j = 0; j < A; ++j) {
-    const float loc = tanhf(x[r * 2 * A + j]);
-    const float sc = (max_std - min_std) * sigmoidf_(x[r * 2 * A + A + j] + 2.f) + min_std;
-    const float d = action[r * A + j] - loc;
+    const BNormal b = bnormal_loc_scale(x, r * 2 * A + j, r * 2 * A + A + j);
+    const float sc = b.scale(min_std, max_std);
+    const float d = action[r * A + j] - b.loc;
     lp += -(d * d) / (2.f * sc * sc) - logf(sc) - c0;
     h += 0.5f + c0 + logf(sc);
   }
@@ -528,15 +537,14 @@ __global__ void bnormal_logp_ent_bwd(const float* __restrict__ x, const float* _
   if (t >= rows * A) return;
   const long r = t / A;
   const int j = (int)(t % A);
-  const float loc = tanhf(x[r * 2 * A + j]);
-  const float sg = sigmoidf_(x[r * 2 * A + A + j] + 2.f);
-  const float sc = (max_std - min_std) * sg + min_std;
-  const float d = action[r * A + j] - loc;
+  const BNormal b = bnormal_loc_scale(x, r * 2 * A + j, r * 2 * A + A + j);
+  const float sc = b.scale(min_std, max_std);
+  const float d = action[r * A + j] - b.loc;
   const float gl = glogp ? glogp[r] : 0.f, ge = gent ? gent[r] : 0.f;
   const float d_loc = gl * d / (sc * sc);
   const float d_sc = gl * (d * d / (sc * sc * sc) - 1.f / sc) + ge / sc;
-  dx[r * 2 * A + j] = d_loc * (1.f - loc * loc);
-  dx[r * 2 * A + A + j] = d_sc * (max_std - min_std) * sg * (1.f - sg);
+  dx[r * 2 * A + j] = d_loc * (1.f - b.loc * b.loc);
+  dx[r * 2 * A + A + j] = d_sc * (max_std - min_std) * b.sg * (1.f - b.sg);
 }
 
 // ---------------------------------------------------------------- Bernoulli(logits) continue head, 1 logit/row
@@ -602,151 +610,128 @@ __global__ void gru_bwd(const float* __restrict__ gates, const float* __restrict
   dh[t] = accumulate_dh ? dh[t] + v : v;
 }
 
-int team_pow2(int K) { return K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64; }
-int blocks_for(long n, int per) { long b = (n + per - 1) / per; return (int)b; }
+// ---------------------------------------------------------------- host side
+// n work items (threads, one-wave rows, or whole blocks with per = 1), `per` of them per 256-thread block, on stream s
+template <class Kern, class... Args>
+int launch(Kern kern, long n, int per, sd_stream s, Args... args) {
+  kern<<<sd_cdiv(n, per), 256, 0, (hipStream_t)s>>>(args...);
+  SD_LAUNCH_CHECK();
+  return SD_OK;
+}
+
+// f(T) with the team width of a K-way categorical (the power of two in 8..64 that holds K) as an integral constant
+template <class F>
+int with_team(int K, F f) {
+  if (K < 1 || K > 64) return SD_ESHAPE;
+  if (K <= 8) return f(std::integral_constant<int, 8>());
+  if (K <= 16) return f(std::integral_constant<int, 16>());
+  if (K <= 32) return f(std::integral_constant<int, 32>());
+  return f(std::integral_constant<int, 64>());
+}
+
+// bins of a two-hot row: one wave holds up to 256; the mode sums +- pairs around a centre bin (odd: 1..255)
+bool twohot_bins_ok(int NB, bool odd = false) { return NB >= 1 && NB <= 256 && (!odd || NB % 2 == 1); }
 
 }  // namespace
-
-#define SD_TEAM_SWITCH(T, ...)                      \
-  switch (T) {                                      \
-    case 8: { constexpr int TT = 8; __VA_ARGS__; } break;   \
-    case 16: { constexpr int TT = 16; __VA_ARGS__; } break; \
-    case 32: { constexpr int TT = 32; __VA_ARGS__; } break; \
-    default: { constexpr int TT = 64; __VA_ARGS__; } break; \
-  }
 
 extern "C" int sd_onehot_sample_fwd(const float* logits, float* out, int* index, float* entropy, long groups, int K,
                                     float unimix, uint64_t seed, int stream_id, int step, long group_offset,
                                     const uint64_t* seed_ptr, sd_stream s) {
   if (groups <= 0) return SD_OK;
-  if (K < 1 || K > 64) return SD_ESHAPE;
-  const int T = team_pow2(K);
-  const int grid = blocks_for(groups * T, 256);
-  SD_TEAM_SWITCH(T, onehot_sample_fwd<TT><<<grid, 256, 0, (hipStream_t)s>>>(logits, out, index, entropy, groups, K,
-                                                                          unimix, seed, stream_id, step, group_offset, seed_ptr))
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return with_team(K, [&](auto T) {
+    return launch(onehot_sample_fwd<T.value>, groups * T.value, 256, s, logits, out, index, entropy, groups, K, unimix,
+                  seed, stream_id, step, group_offset, seed_ptr);
+  });
 }
 
 extern "C" int sd_onehot_sample_bwd(const float* logits, const float* dout, float* dlogits, long groups, int K,
                                     float unimix, uint64_t seed, int stream_id, int step, long group_offset,
                                     int accumulate, const uint64_t* seed_ptr, sd_stream s) {
   if (groups <= 0) return SD_OK;
-  if (K < 1 || K > 64) return SD_ESHAPE;
-  const int T = team_pow2(K);
-  const int grid = blocks_for(groups * T, 256);
-  SD_TEAM_SWITCH(T, onehot_sample_bwd<TT><<<grid, 256, 0, (hipStream_t)s>>>(logits, dout, dlogits, groups, K, unimix,
-                                                                          seed, stream_id, step, group_offset,
-                                                                          accumulate, seed_ptr))
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return with_team(K, [&](auto T) {
+    return launch(onehot_sample_bwd<T.value>, groups * T.value, 256, s, logits, dout, dlogits, groups, K, unimix, seed,
+                  stream_id, step, group_offset, accumulate, seed_ptr);
+  });
 }
 
 extern "C" int sd_onehot_logp_ent_fwd(const float* logits, const float* action, float* logp, float* ent, long rows,
                                       int K, float unimix, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (K < 1 || K > 64) return SD_ESHAPE;
-  const int T = team_pow2(K);
-  const int grid = blocks_for(rows * T, 256);
-  SD_TEAM_SWITCH(T, onehot_logp_ent_fwd<TT><<<grid, 256, 0, (hipStream_t)s>>>(logits, action, logp, ent, rows, K,
-                                                                            unimix))
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return with_team(K, [&](auto T) {
+    return launch(onehot_logp_ent_fwd<T.value>, rows * T.value, 256, s, logits, action, logp, ent, rows, K, unimix);
+  });
 }
 
 extern "C" int sd_onehot_logp_ent_bwd(const float* logits, const float* action, const float* glogp, const float* gent,
                                       float* dlogits, long rows, int K, float unimix, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (K < 1 || K > 64) return SD_ESHAPE;
-  const int T = team_pow2(K);
-  const int grid = blocks_for(rows * T, 256);
-  SD_TEAM_SWITCH(T, onehot_logp_ent_bwd<TT><<<grid, 256, 0, (hipStream_t)s>>>(logits, action, glogp, gent, dlogits,
-                                                                            rows, K, unimix))
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return with_team(K, [&](auto T) {
+    return launch(onehot_logp_ent_bwd<T.value>, rows * T.value, 256, s, logits, action, glogp, gent, dlogits, rows, K,
+                  unimix);
+  });
 }
 
 extern "C" int sd_kl_fwd(const float* post, const float* prior, float* kl_row, float* dyn, float* rep, float free_nats,
                          int rows, int S, int K, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (K < 1 || K > 64) return SD_ESHAPE;
-  const int T = team_pow2(K);
-  const int grid = rows < 4096 ? rows : 4096;
-  SD_TEAM_SWITCH(T, kl_fwd<TT><<<grid, 256, 0, (hipStream_t)s>>>(post, prior, kl_row, dyn, rep, free_nats, rows, S, K))
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return with_team(K, [&](auto T) {  // a block per row, grid-strided past 4096 rows
+    return launch(kl_fwd<T.value>, rows < 4096 ? rows : 4096, 1, s, post, prior, kl_row, dyn, rep, free_nats, rows, S,
+                  K);
+  });
 }
 
 extern "C" int sd_kl_bwd(const float* post, const float* prior, const float* kl_row, const float* g_rep,
                          const float* g_dyn, float free_nats, float* d_post, float* d_prior, int rows, int S, int K,
                          int acc_post, int acc_prior, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (K < 1 || K > 64) return SD_ESHAPE;
-  const int T = team_pow2(K);
-  const int grid = blocks_for((long)rows * S * T, 256);
-  SD_TEAM_SWITCH(T, kl_bwd<TT><<<grid, 256, 0, (hipStream_t)s>>>(post, prior, kl_row, g_rep, g_dyn, free_nats, d_post,
-                                                               d_prior, rows, S, K, acc_post, acc_prior))
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return with_team(K, [&](auto T) {
+    return launch(kl_bwd<T.value>, (long)rows * S * T.value, 256, s, post, prior, kl_row, g_rep, g_dyn, free_nats,
+                  d_post, d_prior, rows, S, K, acc_post, acc_prior);
+  });
 }
 
 extern "C" int sd_twohot_mode(const float* logits, const float* bins, float* out, long rows, int NB, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (NB < 1 || NB > 256 || NB % 2 == 0) return SD_ESHAPE;
-  twohot_mode_kernel<<<blocks_for(rows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, out, rows, NB);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  if (!twohot_bins_ok(NB, true)) return SD_ESHAPE;
+  return launch(twohot_mode_kernel, rows, 4, s, logits, bins, out, rows, NB);
 }
 
 extern "C" int sd_twohot_mode_bwd(const float* logits, const float* bins, const float* dout, float* dlogits, long rows,
                                   int NB, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (NB > 255 || NB < 1 || NB % 2 == 0) return SD_ESHAPE;
-  twohot_mode_bwd_kernel<<<blocks_for(rows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, dout, dlogits, rows, NB);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  if (!twohot_bins_ok(NB, true)) return SD_ESHAPE;
+  return launch(twohot_mode_bwd_kernel, rows, 4, s, logits, bins, dout, dlogits, rows, NB);
 }
 
 extern "C" int sd_twohot_logp_fwd(const float* logits, const float* bins, const float* target, float* logp, long rows,
                                   int NB, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (NB < 1 || NB > 256) return SD_ESHAPE;
-  twohot_logp_fwd<<<blocks_for(rows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, target, logp, rows, NB);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  if (!twohot_bins_ok(NB)) return SD_ESHAPE;
+  return launch(twohot_logp_fwd, rows, 4, s, logits, bins, target, logp, rows, NB);
 }
 
 extern "C" int sd_twohot_logp_bwd(const float* logits, const float* bins, const float* target, const float* glogp,
                                   float* dlogits, long rows, int NB, int accumulate, sd_stream s) {
   if (rows <= 0) return SD_OK;
-  if (NB < 1 || NB > 256) return SD_ESHAPE;
-  twohot_logp_bwd<<<blocks_for(rows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, target, glogp, dlogits, rows, NB,
-                                                                    accumulate);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  if (!twohot_bins_ok(NB)) return SD_ESHAPE;
+  return launch(twohot_logp_bwd, rows, 4, s, logits, bins, target, glogp, dlogits, rows, NB, accumulate);
 }
 
 extern "C" int sd_repval_loss_fwd(const float* logits, const float* bins, const float* ret, const float* slow,
                                   const float* last, float* row_loss, int B, int Tl, int Tr, int NB, sd_stream s) {
   if (B <= 0 || Tr <= 0) return SD_OK;
-  if (NB < 1 || NB > 256 || Tr > Tl) return SD_ESHAPE;
-  const long rows = (long)B * Tr;
-  repval_fwd_kernel<<<blocks_for(rows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, ret, slow, last, row_loss, rows, Tl,
-                                                                      Tr, NB);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  if (!twohot_bins_ok(NB) || Tr > Tl) return SD_ESHAPE;
+  return launch(repval_fwd_kernel, (long)B * Tr, 4, s, logits, bins, ret, slow, last, row_loss, (long)B * Tr, Tl, Tr,
+                NB);
 }
 
 extern "C" int sd_repval_loss_bwd(const float* logits, const float* bins, const float* ret, const float* slow,
                                   const float* last, const float* gscale, float inv_n, float* dlogits, int B, int Tl,
                                   int Tr, int NB, sd_stream s) {
   if (B <= 0) return SD_OK;
-  if (NB < 1 || NB > 256 || !gscale || Tr > Tl) return SD_ESHAPE;
-  const long lrows = (long)B * Tl;
-  repval_bwd_kernel<<<blocks_for(lrows, 4), 256, 0, (hipStream_t)s>>>(logits, bins, ret, slow, last, gscale, inv_n,
-                                                                       dlogits, lrows, Tl, Tr, NB);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  if (!twohot_bins_ok(NB) || !gscale || Tr > Tl) return SD_ESHAPE;
+  return launch(repval_bwd_kernel, (long)B * Tl, 4, s, logits, bins, ret, slow, last, gscale, inv_n, dlogits,
+                (long)B * Tl, Tl, Tr, NB);
 }
 
 extern "C" int sd_imag_ac_loss_fwd(const float* vl, const float* bins, const float* ret, const float* slow,
@@ -754,11 +739,9 @@ extern "C" int sd_imag_ac_loss_fwd(const float* vl, const float* bins, const flo
                                    const float* ent, float coef, long N, int H, int H1, int NB, float* rows_v,
                                    float* rows_p, float* adv, sd_stream s) {
   if (N <= 0 || H <= 0) return SD_OK;
-  if (NB < 1 || NB > 256 || H1 <= H) return SD_ESHAPE;
-  imag_ac_fwd_kernel<<<blocks_for(N * H, 4), 256, 0, (hipStream_t)s>>>(vl, bins, ret, slow, w, val, scale, logpi, ent,
-                                                                       coef, N, H, H1, NB, rows_v, rows_p, adv);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  if (!twohot_bins_ok(NB) || H1 <= H) return SD_ESHAPE;
+  return launch(imag_ac_fwd_kernel, N * H, 4, s, vl, bins, ret, slow, w, val, scale, logpi, ent, coef, N, H, H1, NB,
+                rows_v, rows_p, adv);
 }
 
 extern "C" int sd_imag_ac_loss_bwd(const float* vl, const float* bins, const float* ret, const float* slow,
@@ -766,79 +749,58 @@ extern "C" int sd_imag_ac_loss_bwd(const float* vl, const float* bins, const flo
                                    float spolicy, float svalue, float coef, long N, int H, int H1, int NB, float* dvl,
                                    float* dlogpi, float* dent, sd_stream s) {
   if (N <= 0 || H <= 0) return SD_OK;
-  if (NB < 1 || NB > 256 || H1 <= H) return SD_ESHAPE;
-  imag_ac_bwd_kernel<<<blocks_for(N * H, 4), 256, 0, (hipStream_t)s>>>(vl, bins, ret, slow, w, adv, gpolicy, gvalue,
-                                                                       spolicy, svalue, coef, 1.f / (float)(N * H), N,
-                                                                       H, H1, NB, dvl, dlogpi, dent);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  if (!twohot_bins_ok(NB) || H1 <= H) return SD_ESHAPE;
+  return launch(imag_ac_bwd_kernel, N * H, 4, s, vl, bins, ret, slow, w, adv, gpolicy, gvalue, spolicy, svalue, coef,
+                1.f / (float)(N * H), N, H, H1, NB, dvl, dlogpi, dent);
 }
 
 extern "C" int sd_bnormal_sample(const float* x, float* action, long rows, int A, float min_std, float max_std,
                                  uint64_t seed, int stream_id, int step, long row_offset, const uint64_t* seed_ptr,
                                  sd_stream s) {
   if (rows <= 0 || A <= 0) return SD_OK;
-  bnormal_sample<<<blocks_for(rows * A, 256), 256, 0, (hipStream_t)s>>>(x, action, rows, A, min_std, max_std, seed,
-                                                                        stream_id, step, row_offset, seed_ptr);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return launch(bnormal_sample, rows * A, 256, s, x, action, rows, A, min_std, max_std, seed, stream_id, step,
+                row_offset, seed_ptr);
 }
 
 extern "C" int sd_bnormal_sample_bwd(const float* d_action_norm, const float* x, const float* action, float* dx,
                                      long rows, int A, float min_std, float max_std, uint64_t seed, int stream_id,
                                      int step, long row_offset, const uint64_t* seed_ptr, sd_stream s) {
   if (rows <= 0 || A <= 0) return SD_OK;
-  bnormal_sample_bwd<<<blocks_for(rows * A, 256), 256, 0, (hipStream_t)s>>>(
-      d_action_norm, x, action, dx, rows, A, min_std, max_std, seed, stream_id, step, row_offset, seed_ptr);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return launch(bnormal_sample_bwd, rows * A, 256, s, d_action_norm, x, action, dx, rows, A, min_std, max_std, seed,
+                stream_id, step, row_offset, seed_ptr);
 }
 
 extern "C" int sd_bnormal_logp_ent_fwd(const float* x, const float* action, float* logp, float* ent, long rows, int A,
                                        float min_std, float max_std, sd_stream s) {
   if (rows <= 0 || A <= 0) return SD_OK;
-  bnormal_logp_ent_fwd<<<blocks_for(rows, 256), 256, 0, (hipStream_t)s>>>(x, action, logp, ent, rows, A, min_std,
-                                                                          max_std);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return launch(bnormal_logp_ent_fwd, rows, 256, s, x, action, logp, ent, rows, A, min_std, max_std);
 }
 
 extern "C" int sd_bnormal_logp_ent_bwd(const float* x, const float* action, const float* glogp, const float* gent,
                                        float* dx, long rows, int A, float min_std, float max_std, sd_stream s) {
   if (rows <= 0 || A <= 0) return SD_OK;
-  bnormal_logp_ent_bwd<<<blocks_for(rows * A, 256), 256, 0, (hipStream_t)s>>>(x, action, glogp, gent, dx, rows, A,
-                                                                              min_std, max_std);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return launch(bnormal_logp_ent_bwd, rows * A, 256, s, x, action, glogp, gent, dx, rows, A, min_std, max_std);
 }
 
 extern "C" int sd_bernoulli_fwd(const float* logit, const float* value, float* logp, float* mean, long rows,
                                 sd_stream s) {
   if (rows <= 0) return SD_OK;
-  bernoulli_fwd<<<blocks_for(rows, 256), 256, 0, (hipStream_t)s>>>(logit, value, logp, mean, rows);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return launch(bernoulli_fwd, rows, 256, s, logit, value, logp, mean, rows);
 }
 
 extern "C" int sd_bernoulli_bwd(const float* logit, const float* value, const float* glogp, float* dlogit, long rows,
                                 sd_stream s) {
   if (rows <= 0) return SD_OK;
-  bernoulli_bwd<<<blocks_for(rows, 256), 256, 0, (hipStream_t)s>>>(logit, value, glogp, dlogit, rows);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return launch(bernoulli_bwd, rows, 256, s, logit, value, glogp, dlogit, rows);
 }
 
 extern "C" int sd_gru_fwd(const float* gates, const float* h, float* out, long M, int G, int Dg, sd_stream s) {
   if (M <= 0) return SD_OK;
-  gru_fwd<<<blocks_for(M * G * Dg, 256), 256, 0, (hipStream_t)s>>>(gates, h, out, M, G, Dg);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return launch(gru_fwd, M * G * Dg, 256, s, gates, h, out, M, G, Dg);
 }
 
 extern "C" int sd_gru_bwd(const float* gates, const float* h, const float* dout, float* dgates, float* dh, long M, int G,
                           int Dg, int accumulate_dh, sd_stream s) {
   if (M <= 0) return SD_OK;
-  gru_bwd<<<blocks_for(M * G * Dg, 256), 256, 0, (hipStream_t)s>>>(gates, h, dout, dgates, dh, M, G, Dg, accumulate_dh);
-  SD_LAUNCH_CHECK();
-  return SD_OK;
+  return launch(gru_bwd, M * G * Dg, 256, s, gates, h, dout, dgates, dh, M, G, Dg, accumulate_dh);
 }

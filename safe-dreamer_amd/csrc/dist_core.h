@@ -34,6 +34,19 @@ SD_DEV float unimix_backward(float d_nl, float p, float pp, float nl, bool act, 
   return act ? p * (d_p - sp) : 0.f;
 }
 
+// The smallest index among the team's lanes that hold its largest value (torch max(dim): the first maximum), on every
+// lane. Inactive lanes pass a value below every active one and index 0x7fffffff.
+template <int T>
+SD_DEV int team_first_max(float best, int bi) {
+#pragma unroll
+  for (int o = T / 2; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  }
+  return bi;
+}
+
 template <int T>
 SD_DEV void st_soft(float nl, float g, bool act, float& ys, int& idx, int lane_in_team) {
   const float y = act ? nl + g : -INFINITY;
@@ -41,16 +54,7 @@ SD_DEV void st_soft(float nl, float g, bool act, float& ys, int& idx, int lane_i
   const float e = act ? expf(y - m) : 0.f;
   const float s = group_sum<T>(e);
   ys = e / s;
-  // first index of the maximum soft value (torch max(dim) tie-break)
-  float best = act ? ys : -1.f;
-  int bi = act ? lane_in_team : 0x7fffffff;
-#pragma unroll
-  for (int o = T / 2; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
-  idx = bi;
+  idx = team_first_max<T>(act ? ys : -1.f, act ? lane_in_team : 0x7fffffff);  // index of the largest soft value
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 """Bit-identity check between two builds of libsdhip.so (A/B aid): computes the split-bf16 and f32 conv bwd-weight, the
-pooled-gradient bwd-weight on both, the split-bf16 bwd-data, the fused imagination of the bench agent (random init,
-seed 0) and the parameters after two eager updates of that agent on the bench's synthetic buffer, on fixed inputs,
-with the library SDHIP_LIB points at, and saves them to argv[1]; `python tools/lib_bitcheck.py cmp a.npz b.npz` reports whether every array is bit-identical."""
+pooled-gradient bwd-weight on both, the split-bf16 bwd-data, every output of the distribution-head kernels (csrc/dist.hip)
+over the case tables of tests/rowop_models.py, the fused imagination of the bench agent (random init, seed 0) and the
+parameters after two eager updates of that agent on the bench's synthetic buffer, on fixed inputs, with the library
+SDHIP_LIB points at, and saves them to argv[1]; `python tools/lib_bitcheck.py cmp a.npz b.npz` reports whether every array is bit-identical."""
 import os
 import sys
 
@@ -11,10 +12,36 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "safe-dreamer_amd"), os.path.join(ROOT, "tests")]
 
 
+def rowops(res):
+    """every array the float64 tests of csrc/dist.hip look at, over their full case tables (each dispatch arm)"""
+    import rowop_models as rm
+    import test_gpu_rowops_f64 as t
+    for fam, fn, cases in (("sample", t.run_sample, rm.TEAM_CASES), ("logp", t.run_logp, rm.TEAM_CASES),
+                           ("kl", lambda c: t.run_kl(c)[0], rm.KL_CASES), ("twohot", t.run_twohot, rm.TWOHOT_CASES),
+                           ("repval", t.run_repval, rm.REPVAL_CASES), ("imag_ac", t.run_imag_ac, rm.IMAG_AC_CASES),
+                           ("bnormal", t.run_bnormal, rm.BN_CASES), ("bernoulli", t.run_bernoulli, rm.BERN_ROWS),
+                           ("gru", t.run_gru, rm.GRU_CASES)):
+        for c in cases:
+            for k, v in fn(c).items():
+                res[f"{fam}/{getattr(c, 'name', c)}/{k}"] = v
+    # the bounded normal's sampler and its backward, which no run_* above launches (test_gpu_imag_return_kernels.py)
+    import torch
+    import test_gpu_imag_return_kernels as ir
+    from sdreamer import kernels as K
+    for rows, A in ((1, 1), (65, 6), (65, 16)):
+        x, d_an, _ = ir._bn_inputs(rows, A)
+        xd, act = x.cuda(), torch.empty(rows, A, device="cuda")
+        args = (ir.MIN_STD, ir.MAX_STD, ir.BN_SEED, ir.nz.STREAM_ACT, ir.BN_STEP, ir.BN_ROW_OFFSET)
+        K.nat.call("sd_bnormal_sample", K.p(xd), K.p(act), rows, A, *args, 0, K.stream())
+        res[f"bnormal_sample/{rows}x{A}/action"] = act.cpu().numpy()
+        res[f"bnormal_sample/{rows}x{A}/dx"] = K.bnormal_sample_bwd(d_an.cuda(), xd, act, *args).cpu().numpy()
+
+
 def run(out):
     import torch
     from sdreamer import kernels as K
     res = {}
+    rowops(res)
     for ci, co, hw, nb in [(32, 48, 32, 64), (48, 64, 16, 64), (64, 64, 8, 64), (4, 32, 64, 8)]:
         g = torch.Generator().manual_seed(ci * 7 + co)
         x = (torch.rand(nb, hw, hw, ci, generator=g) - 0.5).cuda()
