@@ -380,7 +380,13 @@ __global__ __launch_bounds__(256) void loss_terms_fwd_kernel(sd_loss_terms L, fl
     float acc = 0.f;
     for (long j = threadIdx.x; j < t.n; j += 256) acc += t.x[j];
     const float m = t.coef * (block_sum<256>(acc, red) / (float)t.n);
-    tot = __fadd_rn(tot, __fmul_rn(t.scale, m));
+    {
+      // the product and the sum each round to float32, as `sum(v * scale)` does: __fmul_rn / __fadd_rn are plain
+      // operators to the compiler, which fused them into one fma
+#pragma clang fp contract(off)
+      const float sm = t.scale * m;
+      tot = tot + sm;
+    }
     if (threadIdx.x == 0 && means) means[i] = m;
   }
   if (threadIdx.x == 0) total[0] = tot;
@@ -627,6 +633,7 @@ extern "C" int sd_action_norm(const float* a, float* y, long n, sd_stream s) {
 }
 extern "C" int sd_mask_rows(const float* x, const uint8_t* mask, long mask_stride, float* y, long rows, int width,
                             sd_stream s) {
+  if (width <= 0) return SD_EARG;
   if (rows <= 0) return SD_OK;
   mask_rows_kernel<<<nb(rows * width), 256, 0, (hipStream_t)s>>>(x, mask, mask_stride, y, rows, width);
   SD_LAUNCH_CHECK();
@@ -652,6 +659,7 @@ extern "C" int sd_colstats(const float* x, int R, int C, float* mean, float* std
 }
 extern "C" int sd_standardize(const float* x, const float* mean, const float* stdv, float* y, long R, int C, float eps,
                               sd_stream s) {
+  if (C <= 0) return SD_EARG;
   if (R <= 0) return SD_OK;
   standardize_kernel<<<nb(R * C), 256, 0, (hipStream_t)s>>>(x, mean, stdv, y, R, C, eps);
   SD_LAUNCH_CHECK();
@@ -666,6 +674,8 @@ extern "C" int sd_standardize_bwd(const float* x, const float* mean, const float
 }
 extern "C" int sd_barlow_loss(const float* c, int E, float lambd, float* partial, int nblocks, float* loss,
                               sd_stream s) {
+  if (!c || !partial || !loss) return SD_EARG;
+  if (E <= 0 || nblocks <= 0) return SD_ESHAPE;
   barlow_partial<<<nblocks, 256, 0, (hipStream_t)s>>>(c, E, lambd, partial);
   SD_LAUNCH_CHECK();
   barlow_final<<<1, 256, 0, (hipStream_t)s>>>(partial, nblocks, lambd, loss);
@@ -703,6 +713,7 @@ extern "C" int sd_barlow_dist_dx(const float* x1, const float* dn1, const float*
   return SD_OK;
 }
 extern "C" int sd_barlow_dc(const float* c, const float* g, float* dc, int E, float lambd, sd_stream s) {
+  if (E <= 0) return SD_ESHAPE;
   barlow_dc<<<nb((long)E * E), 256, 0, (hipStream_t)s>>>(c, g, dc, E, lambd);
   SD_LAUNCH_CHECK();
   return SD_OK;
@@ -765,6 +776,7 @@ extern "C" int sd_infonce_fwd(const float* logits, long ld, int n, int ncol, lon
 extern "C" int sd_infonce_bwd(const float* logits, long ld, int n, int ncol, long label_off, const float* lse,
                               const float* g, float scale, float* dlogits, sd_stream s) {
   if (n <= 0) return SD_OK;
+  if (label_off < 0 || label_off + n > ncol) return SD_EARG;
   infonce_bwd_kernel<<<nb((long)n * ncol), 256, 0, (hipStream_t)s>>>(logits, ld, n, ncol, label_off, lse, g, scale,
                                                                      dlogits);
   SD_LAUNCH_CHECK();
