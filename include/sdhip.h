@@ -526,6 +526,29 @@ int sd_patch_grad(const float* dimg, const int* offsets, float* dpatch, float* p
                   sd_stream stream);
 int sd_patch_step(float* patch, const float* dpatch, float* m, float* v, int* step, const float* base, float lr,
                   float beta1, float beta2, float adam_eps, float linf_eps, long n, sd_stream stream);
+/* The same pair with the patch resampled (expectation over transformations). tf (Nb, SD_PATCH_TF) f32, one row per
+ * image: a00 a01 b0 a10 a11 b1 gain bias. A pixel centre (y, x) has the continuous patch coordinates
+ * u = a00 y + a01 x + b0 (row), v = a10 y + a11 x + b1 (column); the kernels know nothing of angles or scales
+ * (attack.transform_rows builds the rows and refuses a non-finite row or a singular 2 x 2; the kernels stay in bounds
+ * for any row). With i0 = floor(u), j0 = floor(v), fu = u - i0, fv = v - j0 the four taps (i0 + di, j0 + dj) weigh
+ * (1 - fu | fu) (1 - fv | fv); a tap outside [0, ph) x [0, pw) contributes nothing (zero padding of the colour and of
+ * a mask of ones). alpha = the sum of the in-range weights, q_c = the same sum over P(patch[tap, c]) with
+ * P(p) = clamp(gain (p - 0.5) + 0.5 + bias, 0, 1), evaluated as gain p + (0.5 - 0.5 gain + bias).
+ * apply_affine: out_c = q_c + (1 - alpha) in_c, img / enc written as sd_patch_apply writes them, one launch. alpha = 0
+ *   gives the bits of sd_u8_image_inputs; an identity row (a00 = a11 = 1, a01 = a10 = 0, b = -offset, gain 1, bias 0)
+ *   the bits of sd_patch_apply.
+ * grad_affine: dpatch[i, j, c] = sum_n P'_n(patch[i, j, c]) sum_(y, x) w_n(y, x -> i, j) dimg[n, y, x, c], w the
+ *   forward's weight of tap (i, j) (the same f32 expressions), P' = gain where 0 <= gain p + (...) <= 1, else 0
+ *   (patch == NULL: P' = gain, the clamp taken as inactive, and no TV term). One lane per patch element; per image the
+ *   pixels of the image-space bounding box of the lane's 2 x 2 patch-coordinate square in row-major order, the images
+ *   and chunks summed as in sd_patch_grad (part sized alike), the TV term and tv[0] as there. An identity row gives
+ *   the bits of sd_patch_grad. */
+#define SD_PATCH_TF 8
+int sd_patch_apply_affine(const void* in, int in_u8, const float* patch, const float* tf, float* img, float* enc,
+                          int Nb, int H, int W, int C, int Cp, int ph, int pw, float shift, sd_stream stream);
+int sd_patch_grad_affine(const float* dimg, const float* tf, float* dpatch, float* part, long part_floats,
+                         const float* patch, float w_tv, float* tv, int Nb, int H, int W, int C, int ph, int pw,
+                         sd_stream stream);
 /* symlog (distributions.py:8-9) for MLP-encoder inputs (networks.py:333-334) */
 int sd_symlog(const float* x, float* y, long n, sd_stream stream);
 int sd_fill_gumbel(float* out, long n, uint64_t seed, int stream_id, int step, long offset, sd_stream stream);

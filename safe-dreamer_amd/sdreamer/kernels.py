@@ -865,6 +865,55 @@ def patch_grad(d_image, offsets, patch_hw, patch=None, w_tv=0.0):
     return dpatch, tv
 
 
+_PATCH_TF = nat._define(nat.HEADER, "SD_PATCH_TF")
+
+
+def _patch_rows(tf, Nb):
+    if tf.shape != (Nb, _PATCH_TF) or tf.dtype != torch.float32:
+        raise ValueError(f"transform rows {tuple(tf.shape)} {tf.dtype}: ({Nb}, {_PATCH_TF}) float32 (sdhip.h: a00 a01 b0 "
+                         "a10 a11 b1 gain bias)")
+
+
+def patch_apply_affine(images, patch, tf, Cp=None, shift=0.5, need_f32=True):
+    """patch_apply with the patch resampled: tf (Nb, 8) f32, one row per image (attack.transform_rows; the layout is
+    in sdhip.h) -> (composited f32 image or None, encoder input), one launch (sd_patch_apply_affine)."""
+    _chk(images, patch, tf)
+    Nb, H, W, C = images.shape
+    ph, pw, pc = patch.shape
+    if pc != C or patch.dtype != torch.float32:
+        raise ValueError(f"patch {tuple(patch.shape)} {patch.dtype} for images {tuple(images.shape)}")
+    _patch_rows(tf, Nb)
+    if images.dtype not in (torch.uint8, torch.float32):
+        raise TypeError("patch_apply_affine takes uint8 or float32 images")
+    Cp = (C + 3) // 4 * 4 if Cp is None else Cp
+    f = torch.empty(images.shape, dtype=torch.float32, device=images.device) if need_f32 else None
+    enc = torch.empty(Nb, H, W, Cp, dtype=torch.float32, device=images.device)
+    nat.call("sd_patch_apply_affine", p(_c(images)), int(images.dtype == torch.uint8), p(_c(patch)), p(_c(tf)), p(f),
+             p(enc), Nb, H, W, C, Cp, ph, pw, float(shift), stream())
+    return f, enc
+
+
+def patch_grad_affine(d_image, tf, patch_hw, patch=None, w_tv=0.0):
+    """The adjoint of patch_apply_affine in the patch (fixed-order sums: bit-identical on repetition). patch given:
+    the clamp's derivative is taken at it, w_tv * the TV gradient is added and (d_patch, tv (1,)) returned; patch
+    None: the clamp is taken as inactive, -> (d_patch, None)."""
+    Nb, H, W, C = d_image.shape
+    ph, pw = patch_hw
+    _chk(d_image, tf, patch)
+    if d_image.dtype != torch.float32:
+        raise ValueError("patch_grad_affine: d_image (Nb, H, W, C) f32")
+    _patch_rows(tf, Nb)
+    if patch is not None and (tuple(patch.shape) != (ph, pw, C) or patch.dtype != torch.float32):
+        raise ValueError("patch_grad_affine: patch must be (ph, pw, C) f32")
+    dev = d_image.device
+    dpatch = torch.empty(ph, pw, C, dtype=torch.float32, device=dev)
+    part = torch.empty(-(-Nb // _PATCH_CHUNK) * ph * pw * C, dtype=torch.float32, device=dev)
+    tv = torch.empty(1, dtype=torch.float32, device=dev) if patch is not None else None
+    nat.call("sd_patch_grad_affine", p(_c(d_image)), p(_c(tf)), p(dpatch), p(part), part.numel(),
+             p(_c(patch) if patch is not None else None), float(w_tv), p(tv), Nb, H, W, C, ph, pw, stream())
+    return dpatch, tv
+
+
 def patch_step(patch, d_patch, m, v, step, lr, base=None, eps=None, betas=(0.9, 0.999), adam_eps=1e-8):
     """One torch.optim.Adam step on `patch` in place (moments m, v and the int32 counter step (1,) on the device),
     then the clamp to [0, 1] and, with eps, to [base - eps, base + eps]; one launch, no host sync."""
