@@ -732,6 +732,17 @@ def conv2d_dgrad_pool_takes(H, W, Co, Ci, kh, kw, pad=None):
 DGRAD_POOL_CALLS = 0  # calls of conv2d_dgrad_pool so far (tests: the update path never makes one)
 
 
+def _pooled_dgrad_dims(who, dpool, amax, w):
+    """checks dpool (Nb, H/2, W/2, Co), amax (uint8, the same shape), w (Co, kh, kw, Ci) -> Nb, H, W, Co, Ci, kh, kw"""
+    Nb, Ho, Wo, Co = dpool.shape
+    _, kh, kw, Ci = w.shape
+    _chk(dpool, amax, w)
+    if amax.shape != dpool.shape or amax.dtype != torch.uint8 or w.shape[0] != Co:
+        raise ValueError(f"{who}: dpool {tuple(dpool.shape)}, amax {tuple(amax.shape)} {amax.dtype}, "
+                         f"w {tuple(w.shape)}")
+    return Nb, 2 * Ho, 2 * Wo, Co, Ci, kh, kw
+
+
 def conv2d_dgrad_pool(dpool, amax, w, pad=None):
     """Input gradient of a pooled stage from the max-pool backward's pooled-resolution gradient dpool (Nb, H/2, W/2,
     Co) and the forward's argmax amax (uint8, same shape): conv_same(expand(dpool, amax), flipped w) -> (Nb, H, W, Ci)
@@ -740,14 +751,8 @@ def conv2d_dgrad_pool(dpool, amax, w, pad=None):
     channels, 5x5, W = 64): the caller then runs pool_rms_bwd + conv2d_dgrad on the channel-padded weight."""
     global DGRAD_POOL_CALLS
     DGRAD_POOL_CALLS += 1
-    Nb, Ho, Wo, Co = dpool.shape
-    _, kh, kw, Ci = w.shape
-    _chk(dpool, amax, w)
-    if amax.shape != dpool.shape or amax.dtype != torch.uint8 or w.shape[0] != Co:
-        raise ValueError(f"conv2d_dgrad_pool: dpool {tuple(dpool.shape)}, amax {tuple(amax.shape)} {amax.dtype}, "
-                         f"w {tuple(w.shape)}")
+    Nb, H, W, Co, Ci, kh, kw = _pooled_dgrad_dims("conv2d_dgrad_pool", dpool, amax, w)
     pad = (kh - 1) // 2 if pad is None else pad
-    H, W = 2 * Ho, 2 * Wo
     if not conv2d_dgrad_pool_takes(H, W, Co, Ci, kh, kw, pad):
         return None
     din = torch.empty(Nb, H, W, Ci, dtype=torch.float32, device=dpool.device)
@@ -795,14 +800,8 @@ def conv2d_dgrad_pooled(dpool, amax, w, pad=None):
     """conv2d_dgrad(expand(dpool, amax), w) bit for bit on the direct split-bf16 kernel, from the pooled-resolution
     gradient dpool (Nb, H/2, W/2, Co) and the forward's argmax: the expanded gradient exists in LDS only. None when the
     shape is outside the kernel's two (conv2d_dgrad_pooled_takes)."""
-    Nb, Ho, Wo, Co = dpool.shape
-    _, kh, kw, Ci = w.shape
-    _chk(dpool, amax, w)
-    if amax.shape != dpool.shape or amax.dtype != torch.uint8 or w.shape[0] != Co:
-        raise ValueError(f"conv2d_dgrad_pooled: dpool {tuple(dpool.shape)}, amax {tuple(amax.shape)} {amax.dtype}, "
-                         f"w {tuple(w.shape)}")
+    Nb, H, W, Co, Ci, kh, kw = _pooled_dgrad_dims("conv2d_dgrad_pooled", dpool, amax, w)
     pad = kh - 1 - (kh - 1) // 2 if pad is None else pad
-    H, W = 2 * Ho, 2 * Wo
     if not conv2d_dgrad_pooled_takes(H, W, Co, Ci, kh, kw, pad):
         return None
     ws = _SPLIT.get(w.data_ptr())
@@ -1007,13 +1006,17 @@ def _film_args(film, Nb, C):
     return _c(gamma), _c(beta), Nb // rows
 
 
+def _stage_outputs(Nb, H, W, C, device):
+    """(y, pooled, amax, rstd) of a pooled stage over (Nb, H, W) images with C output channels, uninitialised"""
+    pooled = torch.empty(Nb, H // 2, W // 2, C, dtype=torch.float32, device=device)
+    amax = torch.empty(Nb, H // 2, W // 2, C, dtype=torch.uint8, device=device)
+    return torch.empty_like(pooled), pooled, amax, torch.empty(Nb, H // 2, W // 2, dtype=torch.float32, device=device)
+
+
 def pool_rms_fwd(x, w, nchw_flat=False, film=None):
     """film = (gamma, beta): the FiLM stage, z = gamma[n // ipc] * norm + beta[n // ipc] before the SiLU"""
     Nb, H, W, C = x.shape
-    pooled = torch.empty(Nb, H // 2, W // 2, C, dtype=torch.float32, device=x.device)
-    amax = torch.empty(Nb, H // 2, W // 2, C, dtype=torch.uint8, device=x.device)
-    y = torch.empty_like(pooled)
-    rstd = torch.empty(Nb, H // 2, W // 2, dtype=torch.float32, device=x.device)
+    y, pooled, amax, rstd = _stage_outputs(Nb, H, W, C, x.device)
     if film is not None:
         gamma, beta, ipc = _film_args(film, Nb, C)
         nat.call("sd_pool_rms_fwd_film", p(_c(x)), p(w), p(gamma), p(beta), ipc, p(pooled), p(amax), p(y), p(rstd),
@@ -1035,10 +1038,7 @@ def conv2d_fwd_pool(x, w, b, nw, nchw_flat=False, film=None):
     the fused kernel. film = (gamma, beta): the same kernels with the FiLM modulation in their epilogue."""
     Nb, H, W, Ci = x.shape
     Co, kh, kw, _ = w.shape
-    pooled = torch.empty(Nb, H // 2, W // 2, Co, dtype=torch.float32, device=x.device)
-    amax = torch.empty(Nb, H // 2, W // 2, Co, dtype=torch.uint8, device=x.device)
-    y = torch.empty_like(pooled)
-    rstd = torch.empty(Nb, H // 2, W // 2, dtype=torch.float32, device=x.device)
+    y, pooled, amax, rstd = _stage_outputs(Nb, H, W, Co, x.device)
     sfx, fa = "", ()
     if film is not None:
         gamma, beta, ipc = _film_args(film, Nb, Co)
@@ -1055,45 +1055,36 @@ def conv2d_fwd_pool(x, w, b, nw, nchw_flat=False, film=None):
     return (y, pooled, amax, rstd) if ok else None
 
 
-def _film_bwd_args(film, Nb, H, W, C, device):
-    gamma, beta, ipc = _film_args(film, Nb, C)
-    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-    fpart = torch.empty(nat.fns["sd_film_grad_floats"](Nb, ipc, H, W, C), dtype=torch.float32, device=device)
-    return gamma, beta, ipc, dgamma, dbeta, fpart
+def _pool_rms_bwd(stem, out_shape, pooled, amax, w, rstd, dy, H, W, dw, nchw_flat, film):
+    """pool_rms_bwd / pool_rms_bwd_compact: entry `stem` (`stem`_film with film) writes the gradient of out_shape"""
+    Nb, Ho, Wo, C = pooled.shape
+    d = torch.empty(out_shape, dtype=torch.float32, device=pooled.device)
+    nb = nat.fns["sd_pool_rms_bwd_blocks"](Nb, H, W)
+    part = torch.empty((nb + nat.fns["sd_colsum_chunks"](nb)) * C, dtype=torch.float32, device=pooled.device)
+    if film is not None:
+        gamma, beta, ipc = _film_args(film, Nb, C)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+        fpart = torch.empty(nat.fns["sd_film_grad_floats"](Nb, ipc, H, W, C), dtype=torch.float32, device=pooled.device)
+        nat.call(stem + "_film", p(pooled), p(amax), p(w), p(gamma), p(beta), ipc, p(rstd), p(_c(dy)), p(d), p(dw),
+                 p(part), p(dgamma), p(dbeta), p(fpart), Nb, H, W, C, int(nchw_flat), 1, stream())
+        return d, dgamma, dbeta
+    nat.call(stem, p(pooled), p(amax), p(w), p(rstd), p(_c(dy)), p(d), p(dw), p(part), Nb, H, W, C, int(nchw_flat), 1,
+             stream())
+    return d
 
 
 def pool_rms_bwd_compact(pooled, amax, w, rstd, dy, dw, nchw_flat=False, film=None):
     """pool_rms_bwd writing the pooled-resolution gradient (Nb, H/2, W/2, C) instead of the scattered conv gradient.
     film = (gamma, beta): returns (dpool, dgamma, dbeta)."""
     Nb, Ho, Wo, C = pooled.shape
-    H, W = 2 * Ho, 2 * Wo
-    dp = torch.empty_like(pooled)
-    nb = nat.fns["sd_pool_rms_bwd_blocks"](Nb, H, W)
-    part = torch.empty((nb + nat.fns["sd_colsum_chunks"](nb)) * C, dtype=torch.float32, device=pooled.device)
-    if film is not None:
-        gamma, beta, ipc, dgamma, dbeta, fpart = _film_bwd_args(film, Nb, H, W, C, pooled.device)
-        nat.call("sd_pool_rms_bwd_compact_film", p(pooled), p(amax), p(w), p(gamma), p(beta), ipc, p(rstd), p(_c(dy)),
-                 p(dp), p(dw), p(part), p(dgamma), p(dbeta), p(fpart), Nb, H, W, C, int(nchw_flat), 1, stream())
-        return dp, dgamma, dbeta
-    nat.call("sd_pool_rms_bwd_compact", p(pooled), p(amax), p(w), p(rstd), p(_c(dy)), p(dp), p(dw), p(part), Nb, H, W,
-             C, int(nchw_flat), 1, stream())
-    return dp
+    return _pool_rms_bwd("sd_pool_rms_bwd_compact", (Nb, Ho, Wo, C), pooled, amax, w, rstd, dy, 2 * Ho, 2 * Wo, dw,
+                         nchw_flat, film)
 
 
 def pool_rms_bwd(pooled, amax, w, rstd, dy, H, W, dw, nchw_flat=False, film=None):
     """film = (gamma, beta): returns (dx, dgamma, dbeta)"""
     Nb, Ho, Wo, C = pooled.shape
-    dx = torch.empty(Nb, H, W, C, dtype=torch.float32, device=pooled.device)
-    nb = nat.fns["sd_pool_rms_bwd_blocks"](Nb, H, W)
-    part = torch.empty((nb + nat.fns["sd_colsum_chunks"](nb)) * C, dtype=torch.float32, device=pooled.device)
-    if film is not None:
-        gamma, beta, ipc, dgamma, dbeta, fpart = _film_bwd_args(film, Nb, H, W, C, pooled.device)
-        nat.call("sd_pool_rms_bwd_film", p(pooled), p(amax), p(w), p(gamma), p(beta), ipc, p(rstd), p(_c(dy)), p(dx),
-                 p(dw), p(part), p(dgamma), p(dbeta), p(fpart), Nb, H, W, C, int(nchw_flat), 1, stream())
-        return dx, dgamma, dbeta
-    nat.call("sd_pool_rms_bwd", p(pooled), p(amax), p(w), p(rstd), p(_c(dy)), p(dx), p(dw), p(part), Nb, H, W, C,
-             int(nchw_flat), 1, stream())
-    return dx
+    return _pool_rms_bwd("sd_pool_rms_bwd", (Nb, H, W, C), pooled, amax, w, rstd, dy, H, W, dw, nchw_flat, film)
 
 
 # ------------------------------------------------------------------------------------------------- text conditioning

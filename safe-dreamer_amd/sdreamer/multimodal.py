@@ -6,7 +6,7 @@ Module trees and parameter names follow the reference, so `state_dict()` keys an
 trainable runs on the HIP kernels:
 
   * FiLMConvEncoder: ConvEncoder's fused stage kernels with gamma * x + beta in their epilogue
-    (ops.FilmConvPoolNormFn; gamma / beta one row per batch row, looked up per image);
+    (ops.ConvPoolNormFn with gamma, beta; one row per batch row, looked up per image);
   * TextGate: out = (1 - g) v + g tp[b], the concatenation cat[v, tp] never materialised (ops.GateFirstFn splits
     gate_net.0.weight into its v and tp halves, the tp half a B-row GEMM added per batch row);
   * TextContextEncoder: attention pooling over the token features (one kernel) + proj, eagerly, into a persistent
@@ -25,7 +25,7 @@ from torch import nn
 
 from . import kernels as K
 from . import ops
-from .networks import Act, Conv2d, ConvEncoder, Linear, RMSNorm
+from .networks import Act, Conv2d, ConvEncoder, Linear, RMSNorm, run_conv_stages
 
 TEXT_RESAMPLE_INTERVAL = 64  # training forwards between two text draws (encoder.py:121)
 
@@ -94,17 +94,8 @@ class FiLMConvEncoder(nn.Module):
 
     def forward(self, x, ctx, split=None, pad_shift=None):
         """ctx (B, ctx_dim), one row per x.shape[0] // B consecutive images. split, pad_shift: see
-        ConvEncoder.forward."""
-        n = len(self.depths)
-        for i in range(n):
-            gamma, beta = self.films[i](ctx)
-            x = ops.FilmConvPoolNormFn.apply(x, self.convs[i].weight, self.convs[i].bias, self.norms[i].weight, gamma,
-                                             beta, i == n - 1, pad_shift if i == 0 else None)
-            if i == 0 and n > 1 and split is not None and x.requires_grad:
-                leaf = x.detach().requires_grad_(True)
-                split.append((x, leaf))
-                x = leaf
-        return x
+        networks.run_conv_stages."""
+        return run_conv_stages(x, list(zip(self.convs, self.norms, self.films)), split, pad_shift, ctx)
 
 
 class TextGate(nn.Module):

@@ -307,6 +307,24 @@ def _heads_rest_fused(heads, h0, p0):
     return out
 
 
+def run_conv_stages(x, stages, split=None, pad_shift=None, ctx=None):
+    """x through the encoder stages, each (conv, norm, film): film None (the plain stage) or the stage's FiLM
+    generator, whose (gamma, beta) = film(ctx) is formed right before the stage runs; the last stage flattens in NCHW
+    order. split (a list): the first stage's output is continued as a detached leaf and (output, leaf) appended, so the
+    backward runs as two calls (stages 2.. down to the leaf, then the first stage). pad_shift: x is the raw image
+    whose gradient is wanted; the first stage forms x - pad_shift, channel-padded, itself (ops._stage_input) and
+    returns the gradient in the image's own shape."""
+    n = len(stages)
+    for i, (conv, norm, film) in enumerate(stages):
+        x = ops.ConvPoolNormFn.apply(x, conv.weight, conv.bias, norm.weight, i == n - 1, pad_shift if i == 0 else None,
+                                     *(film(ctx) if film is not None else ()))
+        if i == 0 and n > 1 and split is not None and x.requires_grad:
+            leaf = x.detach().requires_grad_(True)
+            split.append((x, leaf))
+            x = leaf
+    return x
+
+
 class ConvEncoder(nn.Module):
     """networks.py:192-234. Input NHWC float in [0, 1] (B*T, 64, 64, 3); output (B*T, C*h*w) in NCHW flatten order."""
 
@@ -331,21 +349,9 @@ class ConvEncoder(nn.Module):
         return [self.layers[4 * i].weight for i in range(1, len(self.depths))]
 
     def forward(self, obs, split=None, pad_shift=None):
-        """split (a list): the first stage's output is continued as a detached leaf and (output, leaf) appended, so
-        the backward runs as two calls (stages 2.. down to the leaf, then the first stage). pad_shift: obs is the raw
-        image whose gradient is wanted; the first stage forms obs - pad_shift, channel-padded, itself (ops._stage_input)
-        and returns the gradient in the image's own shape."""
-        x = obs
-        n = len(self.depths)
-        for i in range(n):
-            conv, norm = self.layers[4 * i], self.layers[4 * i + 2]
-            x = ops.ConvPoolNormFn.apply(x, conv.weight, conv.bias, norm.weight, i == n - 1,
-                                         pad_shift if i == 0 else None)
-            if i == 0 and n > 1 and split is not None and x.requires_grad:
-                leaf = x.detach().requires_grad_(True)
-                split.append((x, leaf))
-                x = leaf
-        return x
+        """split, pad_shift: see run_conv_stages"""
+        stages = [(self.layers[4 * i], self.layers[4 * i + 2], None) for i in range(len(self.depths))]
+        return run_conv_stages(obs, stages, split, pad_shift)
 
 
 class MultiEncoder(nn.Module):

@@ -354,25 +354,26 @@ def _stage_input(x, w, pad_shift):
     return x, (w if x.shape[-1] == w.shape[-1] else _pad_last(w, x.shape[-1]))
 
 
-def _pooled_dx(ctx, x, w):
-    """True when the stage's input gradient is wanted and comes from the pooled gradient (k.conv2d_dgrad_pool): a
-    channel-padded input on a shape both pooled-gradient kernels take."""
+def _stage_route(need_dx, x, w):
+    """The one place a stage's backward route is chosen, for the conv input x (after _stage_input) and the weight w as
+    the module holds it: "first", "x3" or "full".
+    first: the first stage. Its f32 / split-bf16 pooled bwd-weight (k.conv2d_wgrad_pool) takes the shape, and the input
+    gradient is not wanted or x is channel-padded and k.conv2d_dgrad_pool takes it: both expand the pooled gradient +
+    argmax themselves.
+    x3: stages 2-3. The split-bf16 bwd-weight has its pooled form at its plan (k.conv2d_wgrad_pooled), and the input
+    gradient is not wanted or has one too (k.conv2d_dgrad_pooled); every gradient is the full route's bit for bit.
+    full: through the full-resolution conv gradient (3/4 zeros), which the other two never write or read."""
     Nb, H, W, Cx = x.shape
     Co, kh, kw, Ci = w.shape
-    return (ctx.needs_input_grad[0] and Cx != Ci and POOL_COMPACT and k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0
-            and k.conv2d_dgrad_pool_takes(H, W, Co, Ci, kh, kw))
-
-
-def _pooled_x3(ctx, x, w):
-    """True when the stage's backward runs the split-bf16 contractions from the pooled gradient (k.conv2d_wgrad_pooled,
-    k.conv2d_dgrad_pooled): its bwd-weight has the pooled form at its plan, and its input gradient is not wanted or has
-    one too. The full-resolution conv gradient (3/4 zeros) is then never written or read; every gradient is the
-    full-resolution route's bit for bit."""
-    Nb, H, W, Cx = x.shape
-    Co, kh, kw, Ci = w.shape
-    if not POOL_COMPACT or k.conv2d_wgrad_pooled_slabs(x, Co, kh, kw) <= 0:
-        return False
-    return not ctx.needs_input_grad[0] or (Cx == Ci and k.conv2d_dgrad_pooled_takes(H, W, Co, Ci, kh, kw))
+    if not POOL_COMPACT:
+        return "full"
+    if k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0 and (
+            not need_dx or (Cx != Ci and k.conv2d_dgrad_pool_takes(H, W, Co, Ci, kh, kw))):
+        return "first"
+    if k.conv2d_wgrad_pooled_slabs(x, Co, kh, kw) > 0 and (
+            not need_dx or (Cx == Ci and k.conv2d_dgrad_pooled_takes(H, W, Co, Ci, kh, kw))):
+        return "x3"
+    return "full"
 
 
 def _stage_dx(ctx, x, w, dconv, dpool, amax, x3=False):
@@ -411,73 +412,28 @@ def _stage_wgrad(x, dconv, dpool, amax, kh, kw, acc):
 
 
 class ConvPoolNormFn(torch.autograd.Function):
-    """One ConvEncoder stage: Conv2dSamePad -> MaxPool2d(2) -> RMSNorm2D -> SiLU (networks.py:201-216), NHWC.
-    Forward on the exact f32 MFMA kernels (the posterior samples depend on it); both backward contractions on the
-    split-bf16 kernels (k.conv2d_wgrad / k.conv2d_dgrad, ~1e-5 relative)."""
+    """One ConvEncoder stage: Conv2dSamePad -> MaxPool2d(2) -> RMSNorm2D -> [gamma * x + beta] -> SiLU
+    (networks.py:201-216; the FiLM stage when gamma / beta are given), NHWC. Forward on the exact f32 MFMA kernels (the
+    posterior samples depend on it); both backward contractions on the split-bf16 kernels (k.conv2d_wgrad /
+    k.conv2d_dgrad, ~1e-5 relative), on the route _stage_route names.
+    gamma / beta are (rows, Co), one row per Nb / rows consecutive images (a batch row's T frames), applied in the same
+    kernels' epilogue; their gradients are returned to autograd (the FiLM generator continues the chain), every
+    parameter gradient is accumulated. With gamma = 1 and beta = 0 every output and gradient equals the plain stage's
+    bit for bit."""
 
     @staticmethod
-    def forward(ctx, x, w, b, nw, nchw_flat, pad_shift=None):
+    def forward(ctx, x, w, b, nw, nchw_flat, pad_shift=None, gamma=None, beta=None):
         # x may carry zero-padded channels (first layer: 3 -> 4); the weight is padded to match
         ctx.raw_c = x.shape[-1] if pad_shift is not None else None
         x, wk = _stage_input(x, w, pad_shift)
-        fused = k.conv2d_fwd_pool(x.contiguous(), wk, b, nw, nchw_flat=nchw_flat) if FUSED_POOL else None
-        if fused is None:
-            conv = k.conv2d_fwd(x.contiguous(), wk, b)
-            fused = k.pool_rms_fwd(conv, nw, nchw_flat=nchw_flat)
-            del conv
-        y, pooled, amax, rstd = fused
-        ctx.save_for_backward(x, w, b, nw, pooled, amax, rstd)
-        ctx.nchw_flat = nchw_flat
-        if nchw_flat:
-            return y.view(y.shape[0], -1)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w, b, nw, pooled, amax, rstd = ctx.saved_tensors
-        Nb, H, W, _ = x.shape
-        Co, kh, kw, Ci = w.shape
-        acc = (grad_buf(w), grad_buf(b), Ci)  # the bwd-weight launches add into the gradients themselves
-        dpool = None
-        first = _pooled_dx(ctx, x, w) or (not ctx.needs_input_grad[0] and POOL_COMPACT and
-                                          k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0)
-        x3 = not first and _pooled_x3(ctx, x, w)
-        if first:
-            # first stage: the bwd-weight kernel (and the input-gradient kernel, when the image's gradient is wanted)
-            # expands the pooled gradient + argmax itself, so the full-resolution conv gradient (3/4 zeros) is never
-            # written or read
-            dpool = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw), nchw_flat=ctx.nchw_flat)
-            k.conv2d_wgrad_pool(x, dpool, amax, kh, kw, acc=acc)
-            dconv = None
-        elif x3:  # later stages: the same, on the split-bf16 kernels of the full-resolution route (bit-identical)
-            dpool = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw), nchw_flat=ctx.nchw_flat)
-            dconv = None
-        else:
-            dconv = k.pool_rms_bwd(pooled, amax, nw, rstd, dy.contiguous(), H, W, grad_buf(nw), nchw_flat=ctx.nchw_flat)
-        _stage_wgrad(x, dconv, dpool if x3 else None, amax, kh, kw, acc)
-        dx = _stage_dx(ctx, x, w, dconv, dpool, amax, x3) if ctx.needs_input_grad[0] else None
-        return dx, None, None, None, None, None
-
-
-class FilmConvPoolNormFn(torch.autograd.Function):
-    """One FiLM encoder stage: Conv2dSamePad -> MaxPool2d(2) -> RMSNorm2D -> gamma * x + beta -> SiLU, NHWC, on
-    ConvPoolNormFn's kernels with the modulation in their epilogue. gamma / beta are (rows, Co), one row per
-    Nb / rows consecutive images (a batch row's T frames); their gradients are returned to autograd (the FiLM
-    generator continues the chain), every parameter gradient is accumulated as in ConvPoolNormFn. With gamma = 1 and
-    beta = 0 every output and gradient equals ConvPoolNormFn's bit for bit."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, nw, gamma, beta, nchw_flat, pad_shift=None):
-        ctx.raw_c = x.shape[-1] if pad_shift is not None else None
-        x, wk = _stage_input(x, w, pad_shift)
-        film = (gamma.contiguous(), beta.contiguous())
+        film = None if gamma is None else (gamma.contiguous(), beta.contiguous())
         fused = k.conv2d_fwd_pool(x.contiguous(), wk, b, nw, nchw_flat=nchw_flat, film=film) if FUSED_POOL else None
         if fused is None:
             conv = k.conv2d_fwd(x.contiguous(), wk, b)
             fused = k.pool_rms_fwd(conv, nw, nchw_flat=nchw_flat, film=film)
             del conv
         y, pooled, amax, rstd = fused
-        ctx.save_for_backward(x, w, b, nw, pooled, amax, rstd, *film)
+        ctx.save_for_backward(x, w, b, nw, pooled, amax, rstd, *(film or ()))
         ctx.nchw_flat = nchw_flat
         if nchw_flat:
             return y.view(y.shape[0], -1)
@@ -485,30 +441,35 @@ class FilmConvPoolNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, w, b, nw, pooled, amax, rstd, gamma, beta = ctx.saved_tensors
+        x, w, b, nw, pooled, amax, rstd, *film = ctx.saved_tensors
+        film = tuple(film) or None
         Nb, H, W, _ = x.shape
         Co, kh, kw, Ci = w.shape
-        acc = (grad_buf(w), grad_buf(b), Ci)
-        film = (gamma, beta)
-        dpool = None
-        first = _pooled_dx(ctx, x, w) or (not ctx.needs_input_grad[0] and POOL_COMPACT and
-                                          k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0)
-        x3 = not first and _pooled_x3(ctx, x, w)
-        if first:
-            dpool, dgamma, dbeta = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw),
-                                                          nchw_flat=ctx.nchw_flat, film=film)
-            k.conv2d_wgrad_pool(x, dpool, amax, kh, kw, acc=acc)
-            dconv = None
-        elif x3:
-            dpool, dgamma, dbeta = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw),
-                                                          nchw_flat=ctx.nchw_flat, film=film)
-            dconv = None
+        need_dx = ctx.needs_input_grad[0]
+        acc = (grad_buf(w), grad_buf(b), Ci)  # the bwd-weight launches add into the gradients themselves
+        route = _stage_route(need_dx, x, w)
+        if route == "full":
+            d = k.pool_rms_bwd(pooled, amax, nw, rstd, dy.contiguous(), H, W, grad_buf(nw), nchw_flat=ctx.nchw_flat,
+                               film=film)
         else:
-            dconv, dgamma, dbeta = k.pool_rms_bwd(pooled, amax, nw, rstd, dy.contiguous(), H, W, grad_buf(nw),
-                                                  nchw_flat=ctx.nchw_flat, film=film)
-        _stage_wgrad(x, dconv, dpool if x3 else None, amax, kh, kw, acc)
-        dx = _stage_dx(ctx, x, w, dconv, dpool, amax, x3) if ctx.needs_input_grad[0] else None
-        return dx, None, None, None, dgamma, dbeta, None, None
+            d = k.pool_rms_bwd_compact(pooled, amax, nw, rstd, dy.contiguous(), grad_buf(nw), nchw_flat=ctx.nchw_flat,
+                                       film=film)
+        d, dgamma, dbeta = d if film else (d, None, None)
+        dconv, dpool = (d, None) if route == "full" else (None, d)
+        if route == "first":
+            k.conv2d_wgrad_pool(x, dpool, amax, kh, kw, acc=acc)
+        _stage_wgrad(x, dconv, dpool if route == "x3" else None, amax, kh, kw, acc)
+        dx = _stage_dx(ctx, x, w, dconv, dpool, amax, route == "x3") if need_dx else None
+        return dx, None, None, None, None, None, dgamma, dbeta
+
+
+class FilmConvPoolNormFn:
+    """The FiLM stage under its earlier name and argument order (gamma, beta before nchw_flat): no function of its
+    own, ConvPoolNormFn with gamma / beta."""
+
+    @staticmethod
+    def apply(x, w, b, nw, gamma, beta, nchw_flat, pad_shift=None):
+        return ConvPoolNormFn.apply(x, w, b, nw, nchw_flat, pad_shift, gamma, beta)
 
 
 class RowBiasSiluFn(torch.autograd.Function):

@@ -212,7 +212,7 @@ def check_plans(nat, Nb, H, W, Ci, Co, k, ups=0):
 # ===================================================================================================== the cases
 @dataclass(frozen=True)
 class StageCase:
-    """One ConvPoolNormFn / FilmConvPoolNormFn call: x (nb, H, W, ci) -> (nb, H/2, W/2, co)."""
+    """One ConvPoolNormFn call, plain or FiLM (ipc): x (nb, H, W, ci) -> (nb, H/2, W/2, co)."""
     name: str
     ci: int
     co: int

@@ -8,6 +8,7 @@ import attack_ref as ar
 import imag_return_ref as irr
 import small_models as sm
 from golden_io import batch, initial, load_case
+from launch_trace import recorded as _recorded
 from test_gpu_act import _inputs
 from test_gpu_dreamer import build_agent
 
@@ -22,29 +23,6 @@ def _cfg(**kw):
                 eot_translations=0)
     base.update(kw)
     return load_attack_config([f"{k}={v}" for k, v in base.items()])
-
-
-class _Launches:
-    """records the name of every C-ABI launch while it sits in nat.PROBES (matches none, so times none)"""
-
-    def __init__(self):
-        self.names = []
-
-    def match(self, name, args):
-        self.names.append(name)
-        return False
-
-
-def _recorded(fn):
-    from sdreamer import _native as nat
-    rec = _Launches()
-    nat.PROBES.append(rec)
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        nat.PROBES.remove(rec)
-    return out, rec.names
 
 
 def _snapshot(ag):

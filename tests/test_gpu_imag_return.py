@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import small_models as sm
+from launch_trace import recorded as _recorded
 from test_imag_return_cpu import cached, upstream
 
 pytestmark = pytest.mark.gpu
@@ -71,29 +72,6 @@ def test_forward_is_the_no_grad_path_bit_for_bit():
     _, ret0b, gs, gd, _ = _product(c, ag)
     _, ret0c, gs2, gd2, _ = _product(c, ag)
     assert torch.equal(ret0b, ret0) and torch.equal(ret0c, ret0) and torch.equal(gs, gs2) and torch.equal(gd, gd2)
-
-
-class _Launches:
-    """records the name of every C-ABI launch while it sits in nat.PROBES (matches none, so times none)"""
-
-    def __init__(self):
-        self.names = []
-
-    def match(self, name, args):
-        self.names.append(name)
-        return False
-
-
-def _recorded(fn):
-    from sdreamer import _native as nat
-    rec = _Launches()
-    nat.PROBES.append(rec)
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        nat.PROBES.remove(rec)
-    return out, rec.names
 
 
 @pytest.mark.parametrize("sink", [False, True], ids=["bare", "grad_sink_scope"])
