@@ -707,6 +707,59 @@ int sd_imagine_noise(const sd_imagine* d, float* noise, float* noise_act, sd_str
  * deter, so only t = H1 - 2 reproduces the run's values (other t overwrite the trajectory: time it, keep no output). */
 int sd_imagine_step_kernel(const sd_imagine* d, int which, int t, sd_stream stream);
 
+/* ---------------------------------------------------------------- fused imagination backward (state gradient)
+ * The serial part of the imagined return's backward (sdreamer/ops.py ImagineReturnFn.backward; the reference
+ * differentiates Dreamer._imagine, dreamer.py:673-692, by autograd): for t = H - 1 .. 0 (H = H1 - 1) the gradient that
+ * has reached step t + 1's state goes back through the prior sample (straight-through, rssm.py:219-220), img_net,
+ * Deter.forward (rssm.py:36-75), the action sample and the actor (networks.py:313-377) into step t's state — 7 launches
+ * per step (csrc/imgbwd.hip), exact-fp32 MFMA contractions with the samplers', the GRU's and the RMSNorm+SiLU backwards
+ * fused into their loaders and epilogues. Every input is a saved or recomputed activation: the samplers' noise is
+ * redrawn from its Philox counters (sd_onehot_sample_bwd's / sd_bnormal_sample_bwd's: streams stream_img / stream_act,
+ * step t, element (row + row_offset) * SK + k / (row + row_offset) * A + j), no sample is drawn again and no
+ * parameter gradient is formed. Fixed summation order: two calls on the same inputs give the same bits.
+ * Shape and frozen parameters: sd_imagine's fields of the same names (the biases are not read). Requirements:
+ * sd_imagine's, and H1 >= 2 (else SD_ESHAPE, from sd_imagine_bwd_ok / _work_floats already and before any launch).
+ * Rows: M = (H1 - 1) * N, step t's rows at t * N (time-major). Layouts:
+ *   feats (H1, N, SK + D), actions (H1, N, A): as sd_imagine_run wrote them;
+ *   x0p, x1p, x2p (M, U): _dyn_in0/1/2's pre-norm outputs; r0, r1, r2 (M): their rstd;
+ *   hp (M, D), rh (M): _dyn_hid's pre-norm output and rstd; gates (M, G, 3, D/G): _dyn_gru's output (sd_gru_fwd's input);
+ *   img_pre[i] (M, U), img_rstd[i] (M): img_net layer i on step t + 1's deter (row t * N + n: the layer that produced
+ *     step t + 1's prior); plogit (M, SK): its logits; act_pre[i] / act_rstd[i] / alogit (M, 2A or A): the actor on
+ *     step t's feat;
+ *   d_stoch (H1, N, SK), d_deter (H1, N, D): in and out. On entry row block t holds the gradient that reaches step t's
+ *     feat from outside the rollout (the heads' input gradient); on exit, for every t in [t_begin, t_end] the total
+ *     gradient with respect to step t's (stoch, deter) — block t + 1 includes the img_net term of step t;
+ *   work: >= sd_imagine_bwd_work_floats(d) floats (transposed weight images, written by every call, and one step's
+ *     intermediates).
+ * t_begin / t_end: walk steps t_end - 1 .. t_begin (t_end <= 0: H1 - 1); chunks run in descending order and share
+ * nothing but d_stoch / d_deter. */
+typedef struct sd_imagine_bwd_desc {
+  int N, H1, D, U, SK, Kd, G, A, act_discrete, actor_layers, img_layers;
+  float eps, unimix, act_unimix, min_std, max_std;
+  uint64_t seed;
+  const uint64_t* seed_ptr;
+  int stream_img, stream_act;
+  long row_offset;
+  const float* Wa[4]; const float* na[4];  /* actor layer i: (U, in_i) (U) */
+  const float* Wao;                        /* actor output: (2A or A, U) */
+  const float *W0, *n0, *W1, *n1, *W2, *n2, *Wh, *nh, *Wg;
+  const float* Wi[4]; const float* ni[4];  /* img_net layer i */
+  const float* Wl;                         /* img_net_logit (SK, U) */
+  const float *feats, *actions;
+  const float *x0p, *x1p, *x2p, *r0, *r1, *r2, *hp, *rh, *gates;
+  const float* img_pre[4]; const float* img_rstd[4];
+  const float* act_pre[4]; const float* act_rstd[4];
+  const float *plogit, *alogit;
+  float *d_stoch, *d_deter;
+  float* work;
+  int t_begin, t_end;
+} sd_imagine_bwd_desc;
+/* 1: the shape is admitted, 0: not (no launch, no device access; pointers are not read) */
+int sd_imagine_bwd_ok(const sd_imagine_bwd_desc* d);
+/* workspace floats; SD_ESHAPE (negative) outside the gate */
+int sd_imagine_bwd_work_floats(const sd_imagine_bwd_desc* d);
+int sd_imagine_bwd(const sd_imagine_bwd_desc* d, sd_stream stream);
+
 /* InfoNCE representation loss (dreamer.py:533-542): cross_entropy(logits - rowmax(logits), arange) on an (n, ncol)
  * row-major logits block (ld floats between rows), row r labelled with column r + label_off (data parallel: local
  * rows against the gathered x2 of every rank). fwd writes per-row losses, the row log-sum-exp (saved for bwd) and the

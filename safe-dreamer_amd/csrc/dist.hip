@@ -83,13 +83,11 @@ __global__ void onehot_sample_bwd(const float* __restrict__ logits, const float*
   if (seed_ptr) seed += *seed_ptr;
   OneHot<T> c;
   if (c.g >= groups) return;
-  c.load(logits, K, unimix);
-  float ys;
-  int idx;
-  c.sample(K, seed, stream, step, group_offset, ys, idx);
+  c.act = c.lt < K;
+  const float l = c.act ? logits[c.g * K + c.lt] : 0.f;
+  const float gn = c.act ? sd_gumbel(seed, stream, step, (uint64_t)(c.g + group_offset) * K + c.lt) : 0.f;
   const float d = c.act ? dout[c.g * K + c.lt] : 0.f;
-  const float sd = group_sum<T>(d * ys);
-  const float dl = c.backward(c.act ? ys * (d - sd) : 0.f, unimix);
+  const float dl = st_sample_backward<T>(l, c.act, K, unimix, gn, d, c.lt);
   if (c.act) dlogits[c.g * K + c.lt] = accumulate ? dlogits[c.g * K + c.lt] + dl : dl;
 }
 
@@ -467,19 +465,7 @@ __global__ void imag_ac_bwd_kernel(const float* __restrict__ vl, const float* __
 }
 
 // ---------------------------------------------------------------- bounded normal actor
-// row r, action dim j of the head output x (rows, 2 A): loc = tanh(x[r, j]), sg = sigmoid(x[r, A + j] + 2) and
-// scale() = (max_std - min_std) sg + min_std
-struct BNormal {
-  float loc, sg;
-  SD_DEV float scale(float min_std, float max_std) const { return (max_std - min_std) * sg + min_std; }
-};
-SD_DEV BNormal bnormal_loc_scale(const float* x, long im, long is) {
-  BNormal b;
-  b.loc = tanhf(x[im]);
-  b.sg = sigmoidf_(x[is] + 2.f);
-  return b;
-}
-
+// (BNormal, bnormal_loc_scale, bnormal_sample_backward: dist_core.h)
 __global__ void bnormal_sample(const float* __restrict__ x, float* __restrict__ action, long rows, int A, float min_std,
                                float max_std, uint64_t seed, uint32_t stream, uint32_t step, long row_offset,
                                const uint64_t* seed_ptr) {
@@ -507,9 +493,7 @@ __global__ void bnormal_sample_bwd(const float* __restrict__ d_an, const float* 
   const int j = (int)(t % A);
   const BNormal b = bnormal_loc_scale(x, r * 2 * A + j, r * 2 * A + A + j);
   const float eps = sd_normal(seed, stream, step, (uint64_t)(r + row_offset) * A + j);
-  const float da = d_an[t] / fmaxf(fabsf(action[t]), 1.f);
-  dx[r * 2 * A + j] = da * (1.f - b.loc * b.loc);
-  dx[r * 2 * A + A + j] = da * eps * (max_std - min_std) * b.sg * (1.f - b.sg);
+  bnormal_sample_backward(b, d_an[t], action[t], eps, min_std, max_std, dx[r * 2 * A + j], dx[r * 2 * A + A + j]);
 }
 
 __global__ void bnormal_logp_ent_fwd(const float* __restrict__ x, const float* __restrict__ action,
@@ -594,20 +578,11 @@ __global__ void gru_bwd(const float* __restrict__ gates, const float* __restrict
   const int gd = (int)(t % D), g = gd / Dg, j = gd % Dg;
   const long base = m * 3 * D + (long)g * 3 * Dg;
   const float ra = gates[base + j], ca = gates[base + Dg + j], ua = gates[base + 2 * Dg + j];
-  const float rs = sigmoidf_(ra);
-  const float c = tanhf(rs * ca);
-  const float u = sigmoidf_(ua - 1.f);
-  const float d = dout[t];
-  const float hv = h[t];
-  const float du = d * (c - hv) * u * (1.f - u);
-  const float dtc = d * u * (1.f - c * c);
-  const float dc = dtc * rs;
-  const float dr = dtc * ca * rs * (1.f - rs);
-  dgates[base + j] = dr;
-  dgates[base + Dg + j] = dc;
-  dgates[base + 2 * Dg + j] = du;
-  const float v = d * (1.f - u);
-  dh[t] = accumulate_dh ? dh[t] + v : v;
+  const GruGrad gg = gru_gate_backward(ra, ca, ua, h[t], dout[t]);
+  dgates[base + j] = gg.dr;
+  dgates[base + Dg + j] = gg.dc;
+  dgates[base + 2 * Dg + j] = gg.du;
+  dh[t] = accumulate_dh ? dh[t] + gg.dh : gg.dh;
 }
 
 // ---------------------------------------------------------------- host side

@@ -76,6 +76,7 @@ def _parse_struct(path, name):
 
 ScanDesc = _parse_struct(HEADER, "sd_rssm_scan")
 ImagineDesc = _parse_struct(HEADER, "sd_imagine")
+ImagineBwdDesc = _parse_struct(HEADER, "sd_imagine_bwd_desc")
 SliceKey = _parse_struct(HEADER, "sd_slice_key")
 
 

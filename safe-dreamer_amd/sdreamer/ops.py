@@ -967,89 +967,192 @@ class ImagineReturnFn(torch.autograd.Function):
     def backward(ctx, d_ret0):
         if d_ret0 is None:
             return (None,) * 7
-        from .rssm import STREAM_ACT, STREAM_IMG
         feats, actions, i_rew, i_val, i_contl = ctx.saved_tensors
         ag, H1, seed, ro = ctx.agent, ctx.H1, ctx.seed, ctx.row_offset
-        r = ag.rssm
-        P = r._p()
-        H, N, F = H1 - 1, feats.shape[1], feats.shape[2]
-        S, Kd, D, U, G, A = r._stoch, r._discrete, r._deter, r._hidden, r._blocks, ag.act_dim
-        SK, Dg, M = S * Kd, D // G, H * N
-        dev, f32 = feats.device, torch.float32
-        e = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)  # noqa: E731
-
-        # ---- batched over all rows: the returns' backward, then the heads' (rows of steps 1 .. H; step 0 has none)
         _mark("begin")
-        d_ret = torch.zeros(N, H, dtype=f32, device=dev)
-        d_ret[:, 0] = d_ret0
-        d_rew, d_val, d_cl = k.lambda_return_bwd(d_ret, i_rew.t(), i_val.t(), i_contl.t(), 1 - 1 / ag.horizon, ag.lamb,
-                                                 time_major=True)
-        d_feat = e(H1, N, F)
-        d_feat[0].zero_()
-        xh = feats[1:].reshape(M, F)
-        dfh = d_feat[1:].view(M, F)
-        for i, (head, bins, d_out) in enumerate(((ag.reward, ag.rbins, d_rew), (ag.cont, None, d_cl),
-                                                 (ag.value, ag.vbins, d_val))):
-            saved, logits = _mlp_recompute(head.mlp._mods, head.last, xh, fast=True)
-            d_out = d_out[1:].reshape(M)
-            d_logits = d_out.view(M, 1) if bins is None else k.twohot_mode_bwd(logits, bins, d_out)
-            d0 = _mlp_input_grad(head.mlp._mods, head.last, saved, d_logits, fast=True)
-            k.gemm(d0, head.mlp._mods[0][0].weight, dfh, beta=1.0 if i else 0.0, fast=True)
-            del saved, logits
-        d_st, d_de = d_feat[..., :SK].contiguous(), d_feat[..., SK:].contiguous()
-        del d_feat, dfh
+        d_st, d_de = _imag_heads_grad(ag, feats, i_rew, i_val, i_contl, d_ret0, H1)
         _mark("heads")
-
-        # ---- batched: every pre-activation of steps 0 .. H - 1 from the saved feats and actions
-        xa = feats[:H].reshape(M, F)
-        h_in = xa[:, SK:].contiguous()
-        a_n = k.action_norm(actions[:H].reshape(M, A))
-        xcat = e(M, 3 * U)
-        x0p, x1p, x2p = k.linear(h_in, P["W0"], P["b0"]), k.linear(xa[:, :SK], P["W1"], P["b1"]), \
-            k.linear(a_n, P["W2"], P["b2"])
-        _, r0 = k.rmsnorm_fwd(x0p, P["n0"], y=xcat[:, :U])
-        _, r1 = k.rmsnorm_fwd(x1p, P["n1"], y=xcat[:, U:2 * U])
-        _, r2 = k.rmsnorm_fwd(x2p, P["n2"], y=xcat[:, 2 * U:])
-        hp = k.mm(xcat, P["Wsh"].t(), bias=P["bh"])
-        k.gemm(h_in.view(M, G, Dg).permute(1, 0, 2), P["Wbd"].transpose(1, 2), hp.view(M, G, Dg).permute(1, 0, 2),
-               beta=1.0)
-        hh, rh = k.rmsnorm_fwd(hp, P["nh"])
-        gates = e(M, 3 * D)
-        k.gemm(hh.view(M, G, Dg).permute(1, 0, 2), P["Wg"].transpose(1, 2), gates.view(M, G, 3 * Dg).permute(1, 0, 2),
-               bias=P["bg"].view(G, 3 * Dg))
-        del xcat, hh
-        img_mods, img_last = r._img_mods()
-        img_saved, plogit = _mlp_recompute(img_mods, img_last, xh[:, SK:])
-        act_mods, act_last = ag.actor.mlp._mods, ag.actor.last
-        act_saved, alogit = _mlp_recompute(act_mods, act_last, xa, fast=True)
-        Wi0, Wa0 = img_mods[0][0].weight, act_mods[0][0].weight
-        dist = ag.config.actor.dist
-        step = lambda x, t: x[t * N:(t + 1) * N]  # noqa: E731
+        rec = _imag_recompute(ag, feats, actions, H1)
         _mark("recompute")
-
-        # ---- serial: d_feat[t + 1] = (d_st[t + 1], d_de[t + 1]) is complete; add step t's part into d_feat[t]
-        for t in reversed(range(H)):
-            dl = k.onehot_sample_bwd(step(plogit, t), d_st[t + 1], Kd, r._unimix_ratio, seed, STREAM_IMG, t, ro * S)
-            k.gemm(_mlp_input_grad(img_mods, img_last, img_saved, dl, (t, N)), Wi0, d_de[t + 1], beta=1.0)
-            d_gates, _ = k.gru_bwd(step(gates, t), step(h_in, t), d_de[t + 1], G, dh=d_de[t], accumulate_dh=True)
-            d_hh = e(N, D)
-            k.gemm(d_gates.view(N, G, 3 * Dg).permute(1, 0, 2), P["Wg"], d_hh.view(N, G, Dg).permute(1, 0, 2))
-            d_hp = k.rmsnorm_bwd(step(hp, t), P["nh"], step(rh, t), d_hh)
-            d_xcat = k.mm(d_hp, P["Wsh"])
-            k.gemm(d_hp.view(N, G, Dg).permute(1, 0, 2), P["Wbd"], d_de[t].view(N, G, Dg).permute(1, 0, 2), beta=1.0)
-            d_x0p = k.rmsnorm_bwd(step(x0p, t), P["n0"], step(r0, t), d_xcat[:, :U])
-            k.gemm(d_x0p, P["W0"], d_de[t], beta=1.0)
-            d_x1p = k.rmsnorm_bwd(step(x1p, t), P["n1"], step(r1, t), d_xcat[:, U:2 * U])
-            k.gemm(d_x1p, P["W1"], d_st[t], beta=1.0)
-            d_x2p = k.rmsnorm_bwd(step(x2p, t), P["n2"], step(r2, t), d_xcat[:, 2 * U:])
-            d_an = k.mm(d_x2p, P["W2"])
-            if ag.act_discrete:  # the normalisation is the identity on a one-hot
-                d_al = k.onehot_sample_bwd(step(alogit, t), d_an, A, float(dist.unimix_ratio), seed, STREAM_ACT, t, ro)
-            else:
-                d_al = k.bnormal_sample_bwd(d_an, step(alogit, t), actions[t], float(dist.min_std),
-                                            float(dist.max_std), seed, STREAM_ACT, t, ro)
-            d_a0 = _mlp_input_grad(act_mods, act_last, act_saved, d_al, (t, N))
-            k.gemm(d_a0, Wa0[:, :SK], d_st[t], beta=1.0)
-            k.gemm(d_a0, Wa0[:, SK:], d_de[t], beta=1.0)
-            _mark("step")
+        if imag_walk_is_fused(ag, rec):
+            _imag_walk_fused(ag, rec, d_st, d_de, seed, ro)
+            _mark("walk")
+        else:
+            _imag_walk_per_op(ag, rec, d_st, d_de, seed, ro)
         return d_st[0].reshape(ctx.stoch_shape), d_de[0], None, None, None, None, None
+
+
+def _imag_heads_grad(ag, feats, i_rew, i_val, i_contl, d_ret0, H1):
+    """Batched over all rows: the returns' backward, then the heads' (rows of steps 1 .. H; step 0 has none) ->
+    d_st (H1, N, SK), d_de (H1, N, D): the gradient that reaches every step's feat from outside the rollout."""
+    r = ag.rssm
+    H, N, F = H1 - 1, feats.shape[1], feats.shape[2]
+    SK, M = r._stoch * r._discrete, H * N
+    dev, f32 = feats.device, torch.float32
+    d_ret = torch.zeros(N, H, dtype=f32, device=dev)
+    d_ret[:, 0] = d_ret0
+    d_rew, d_val, d_cl = k.lambda_return_bwd(d_ret, i_rew.t(), i_val.t(), i_contl.t(), 1 - 1 / ag.horizon, ag.lamb,
+                                             time_major=True)
+    d_feat = torch.empty(H1, N, F, dtype=f32, device=dev)
+    d_feat[0].zero_()
+    xh = feats[1:].reshape(M, F)
+    dfh = d_feat[1:].view(M, F)
+    for i, (head, bins, d_out) in enumerate(((ag.reward, ag.rbins, d_rew), (ag.cont, None, d_cl),
+                                             (ag.value, ag.vbins, d_val))):
+        saved, logits = _mlp_recompute(head.mlp._mods, head.last, xh, fast=True)
+        d_out = d_out[1:].reshape(M)
+        d_logits = d_out.view(M, 1) if bins is None else k.twohot_mode_bwd(logits, bins, d_out)
+        d0 = _mlp_input_grad(head.mlp._mods, head.last, saved, d_logits, fast=True)
+        k.gemm(d0, head.mlp._mods[0][0].weight, dfh, beta=1.0 if i else 0.0, fast=True)
+        del saved, logits
+    return d_feat[..., :SK].contiguous(), d_feat[..., SK:].contiguous()
+
+
+def _imag_recompute(ag, feats, actions, H1):
+    """Batched: every pre-activation of steps 0 .. H - 1 from the saved feats and actions (rows t * N + n), as a dict
+    the two walks read."""
+    r = ag.rssm
+    P = r._p()
+    H, N, F = H1 - 1, feats.shape[1], feats.shape[2]
+    S, Kd, D, U, G, A = r._stoch, r._discrete, r._deter, r._hidden, r._blocks, ag.act_dim
+    SK, Dg, M = S * Kd, D // G, H * N
+    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=feats.device)  # noqa: E731
+    xh = feats[1:].reshape(M, F)
+    xa = feats[:H].reshape(M, F)
+    h_in = xa[:, SK:].contiguous()
+    a_n = k.action_norm(actions[:H].reshape(M, A))
+    xcat = e(M, 3 * U)
+    x0p, x1p, x2p = k.linear(h_in, P["W0"], P["b0"]), k.linear(xa[:, :SK], P["W1"], P["b1"]), \
+        k.linear(a_n, P["W2"], P["b2"])
+    _, r0 = k.rmsnorm_fwd(x0p, P["n0"], y=xcat[:, :U])
+    _, r1 = k.rmsnorm_fwd(x1p, P["n1"], y=xcat[:, U:2 * U])
+    _, r2 = k.rmsnorm_fwd(x2p, P["n2"], y=xcat[:, 2 * U:])
+    hp = k.mm(xcat, P["Wsh"].t(), bias=P["bh"])
+    k.gemm(h_in.view(M, G, Dg).permute(1, 0, 2), P["Wbd"].transpose(1, 2), hp.view(M, G, Dg).permute(1, 0, 2),
+           beta=1.0)
+    hh, rh = k.rmsnorm_fwd(hp, P["nh"])
+    gates = e(M, 3 * D)
+    k.gemm(hh.view(M, G, Dg).permute(1, 0, 2), P["Wg"].transpose(1, 2), gates.view(M, G, 3 * Dg).permute(1, 0, 2),
+           bias=P["bg"].view(G, 3 * Dg))
+    del xcat, hh
+    img_mods, img_last = r._img_mods()
+    img_saved, plogit = _mlp_recompute(img_mods, img_last, xh[:, SK:])
+    act_mods, act_last = ag.actor.mlp._mods, ag.actor.last
+    act_saved, alogit = _mlp_recompute(act_mods, act_last, xa, fast=True)
+    return dict(feats=feats, actions=actions, H=H, N=N, h_in=h_in, x0p=x0p, x1p=x1p, x2p=x2p, r0=r0, r1=r1, r2=r2,
+                hp=hp, rh=rh, gates=gates, img_saved=img_saved, plogit=plogit, act_saved=act_saved, alogit=alogit)
+
+
+def _imag_walk_per_op(ag, rec, d_st, d_de, seed, ro):
+    """The serial walk as per-op launches: d_feat[t + 1] = (d_st[t + 1], d_de[t + 1]) is complete; add step t's part
+    into d_feat[t], t = H - 1 .. 0."""
+    from .rssm import STREAM_ACT, STREAM_IMG
+    r = ag.rssm
+    P = r._p()
+    H, N = rec["H"], rec["N"]
+    S, Kd, D, U, G, A = r._stoch, r._discrete, r._deter, r._hidden, r._blocks, ag.act_dim
+    SK, Dg = S * Kd, D // G
+    actions, h_in, gates, hp, rh = rec["actions"], rec["h_in"], rec["gates"], rec["hp"], rec["rh"]
+    x0p, x1p, x2p, r0, r1, r2 = (rec[n] for n in ("x0p", "x1p", "x2p", "r0", "r1", "r2"))
+    img_saved, plogit, act_saved, alogit = rec["img_saved"], rec["plogit"], rec["act_saved"], rec["alogit"]
+    img_mods, img_last = r._img_mods()
+    act_mods, act_last = ag.actor.mlp._mods, ag.actor.last
+    Wi0, Wa0 = img_mods[0][0].weight, act_mods[0][0].weight
+    dist = ag.config.actor.dist
+    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=d_st.device)  # noqa: E731
+    step = lambda x, t: x[t * N:(t + 1) * N]  # noqa: E731
+    for t in reversed(range(H)):
+        dl = k.onehot_sample_bwd(step(plogit, t), d_st[t + 1], Kd, r._unimix_ratio, seed, STREAM_IMG, t, ro * S)
+        k.gemm(_mlp_input_grad(img_mods, img_last, img_saved, dl, (t, N)), Wi0, d_de[t + 1], beta=1.0)
+        d_gates, _ = k.gru_bwd(step(gates, t), step(h_in, t), d_de[t + 1], G, dh=d_de[t], accumulate_dh=True)
+        d_hh = e(N, D)
+        k.gemm(d_gates.view(N, G, 3 * Dg).permute(1, 0, 2), P["Wg"], d_hh.view(N, G, Dg).permute(1, 0, 2))
+        d_hp = k.rmsnorm_bwd(step(hp, t), P["nh"], step(rh, t), d_hh)
+        d_xcat = k.mm(d_hp, P["Wsh"])
+        k.gemm(d_hp.view(N, G, Dg).permute(1, 0, 2), P["Wbd"], d_de[t].view(N, G, Dg).permute(1, 0, 2), beta=1.0)
+        d_x0p = k.rmsnorm_bwd(step(x0p, t), P["n0"], step(r0, t), d_xcat[:, :U])
+        k.gemm(d_x0p, P["W0"], d_de[t], beta=1.0)
+        d_x1p = k.rmsnorm_bwd(step(x1p, t), P["n1"], step(r1, t), d_xcat[:, U:2 * U])
+        k.gemm(d_x1p, P["W1"], d_st[t], beta=1.0)
+        d_x2p = k.rmsnorm_bwd(step(x2p, t), P["n2"], step(r2, t), d_xcat[:, 2 * U:])
+        d_an = k.mm(d_x2p, P["W2"])
+        if ag.act_discrete:  # the normalisation is the identity on a one-hot
+            d_al = k.onehot_sample_bwd(step(alogit, t), d_an, A, float(dist.unimix_ratio), seed, STREAM_ACT, t, ro)
+        else:
+            d_al = k.bnormal_sample_bwd(d_an, step(alogit, t), actions[t], float(dist.min_std),
+                                        float(dist.max_std), seed, STREAM_ACT, t, ro)
+        d_a0 = _mlp_input_grad(act_mods, act_last, act_saved, d_al, (t, N))
+        k.gemm(d_a0, Wa0[:, :SK], d_st[t], beta=1.0)
+        k.gemm(d_a0, Wa0[:, SK:], d_de[t], beta=1.0)
+        _mark("step")
+
+
+def _imag_bwd_desc(ag, rec, d_st, d_de, seed, ro):
+    """sd_imagine_bwd's descriptor over the recomputed activations (d_st / d_de may be None: the shape questions only);
+    -> (descriptor, the tensors it points to that nothing else holds)"""
+    import ctypes
+    from .rssm import STREAM_ACT, STREAM_IMG
+    r, a = ag.rssm, ag.actor
+    P = r._p()
+    d = k.nat.ImagineBwdDesc()
+    d.N, d.H1, d.D, d.U, d.SK, d.Kd, d.G, d.A = rec["N"], rec["H"] + 1, r._deter, r._hidden, r.flat_stoch, \
+        r._discrete, r._blocks, ag.act_dim
+    d.act_discrete, d.actor_layers, d.img_layers = int(ag.act_discrete), a.mlp.n, r._img_layers
+    dist = ag.config.actor.dist
+    d.eps, d.unimix = k.EPS, r._unimix_ratio
+    if ag.act_discrete:
+        d.act_unimix = float(dist.unimix_ratio)
+    else:
+        d.min_std, d.max_std = float(dist.min_std), float(dist.max_std)
+    d.seed, d.seed_ptr = k.seed_args(seed)
+    d.stream_img, d.stream_act, d.row_offset = STREAM_IMG, STREAM_ACT, int(ro)
+    hold = []
+    for i, (lin, norm) in enumerate(a.mlp._mods):
+        d.Wa[i], d.na[i] = lin.weight.data_ptr(), norm.weight.data_ptr()
+        pre, rstd = rec["act_saved"][i]
+        d.act_pre[i], d.act_rstd[i] = pre.data_ptr(), rstd.data_ptr()
+    wo = a.last.weight.contiguous()
+    hold.append(wo)
+    d.Wao = wo.data_ptr()
+    for n in ("W0", "n0", "W1", "n1", "W2", "n2", "Wh", "nh", "Wg"):
+        setattr(d, n, P[n].data_ptr())
+    mods, last = r._img_mods()
+    for i, (lin, norm) in enumerate(mods):
+        d.Wi[i], d.ni[i] = lin.weight.data_ptr(), norm.weight.data_ptr()
+        pre, rstd = rec["img_saved"][i]
+        d.img_pre[i], d.img_rstd[i] = pre.data_ptr(), rstd.data_ptr()
+    d.Wl = last.weight.data_ptr()
+    d.feats, d.actions = rec["feats"].data_ptr(), rec["actions"].data_ptr()
+    for n in ("x0p", "x1p", "x2p", "r0", "r1", "r2", "hp", "rh", "gates", "plogit", "alogit"):
+        assert rec[n].is_contiguous(), n
+        setattr(d, n, rec[n].data_ptr())
+    if d_st is not None:
+        assert d_st.is_contiguous() and d_de.is_contiguous()
+        d.d_stoch, d.d_deter = d_st.data_ptr(), d_de.data_ptr()
+    return d, hold, ctypes.addressof(d)
+
+
+def imag_walk_is_fused(ag, rec):
+    """The one route decision of the serial walk: the fused imagination's gate and sd_imagine_bwd's own."""
+    if not ag._fused_imag_ok():
+        return False
+    _d, _hold, addr = _imag_bwd_desc(ag, rec, None, None, 0, 0)
+    return k.nat.fns["sd_imagine_bwd_ok"](addr) == 1
+
+
+def _imag_walk_fused(ag, rec, d_st, d_de, seed, ro, chunks=None, work=None):
+    """The serial walk as sd_imagine_bwd (csrc/imgbwd.hip), 7 launches per step. chunks: step boundaries
+    [0, t1, ..., H], walked last chunk first (one ABI call each); work: a workspace to reuse."""
+    d, hold, addr = _imag_bwd_desc(ag, rec, d_st, d_de, seed, ro)
+    nwork = k.nat.fns["sd_imagine_bwd_work_floats"](addr)
+    if nwork < 0:
+        raise k.nat.NativeError(f"sd_imagine_bwd_work_floats failed with status {nwork}")
+    if work is None:
+        work = torch.empty(nwork, dtype=torch.float32, device=d_st.device)
+    assert work.numel() >= nwork
+    d.work = work.data_ptr()
+    bounds = list(chunks) if chunks else [0, rec["H"]]
+    for t0, t1 in reversed(list(zip(bounds[:-1], bounds[1:]))):
+        d.t_begin, d.t_end = int(t0), int(t1)
+        k.nat.call("sd_imagine_bwd", addr, k.stream())
+    return work

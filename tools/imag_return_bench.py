@@ -1,5 +1,5 @@
 """Dreamer.imagined_return forward + backward at B16 L64 H15 (N = 1,024 start rows): device-event times of the whole,
-the forward, the backward's phases (returns + heads, batched recompute, each serial step) and the launches per serial
+the forward, the backward's phases (returns + heads, batched recompute, the serial walk) and the ABI calls per serial
 step; beside them the imagination forward alone and observation_grad. GPU box, repo root:
     python tools/imag_return_bench.py        (under rocprofv3 --kernel-trace --stats for the per-kernel table)"""
 import collections
@@ -89,11 +89,15 @@ def main():
     torch.cuda.synchronize()
     ops.IMAG_RETURN_MARKS = None
     t = [(a, m[1].elapsed_time(n[1]) * 1e3) for a, m, n in zip([n[0] for n in marks[1:]], marks[:-1], marks[1:])]
-    steps = [v for a, v in t if a == "step"]
+    steps = [v for a, v in t if a == "step"]  # the per-op walk marks every step, the fused walk its one ABI call
+    walk = [v for a, v in t if a == "walk"]
     total = sum(v for _, v in t)
+    H = ag.imag_horizon
+    serial = (f"{len(steps)} serial steps {sum(steps):.0f} us (mean {sum(steps) / len(steps):.0f} us, min "
+              f"{min(steps):.0f}, max {max(steps):.0f})" if steps else
+              f"fused serial walk of {H} steps {sum(walk):.0f} us (mean {sum(walk) / H:.0f} us a step)")
     print(f"backward {total:.0f} us: returns + heads {t[0][1]:.0f} us, batched recompute {t[1][1]:.0f} us "
-          f"({100 * t[1][1] / total:.1f} %), {len(steps)} serial steps {sum(steps):.0f} us "
-          f"(mean {sum(steps) / len(steps):.0f} us, min {min(steps):.0f}, max {max(steps):.0f})", flush=True)
+          f"({100 * t[1][1] / total:.1f} %), {serial}", flush=True)
 
     # launches: the whole backward, and one serial step (the difference between horizons H and H - 1)
     def launches(h):
@@ -110,8 +114,9 @@ def main():
 
     a, b = launches(ag.imag_horizon), launches(ag.imag_horizon - 1)
     per_step = a - b
-    print(f"launches in the backward at H {ag.imag_horizon}: {sum(a.values())}; per serial step "
-          f"{sum(per_step.values())}: {dict(per_step)}", flush=True)
+    print(f"ABI calls in the backward at H {ag.imag_horizon}: {sum(a.values())}; per serial step "
+          f"{sum(per_step.values())}: {dict(per_step)} (sd_imagine_bwd: {a['sd_imagine_bwd']} call(s) for all steps; its "
+          f"kernels per step are in the kernel trace)", flush=True)
 
 
 if __name__ == "__main__":
