@@ -364,6 +364,48 @@ int sd_pool_rms_bwd_compact(const float* pooled, const uint8_t* amax, const floa
                             const float* dy, float* dpool, float* dw, float* dw_partial, int Nb, int H, int W, int C,
                             int nchw_flat, int accumulate_dw, sd_stream stream);
 
+/* ---------------------------------------------------------------- wide ConvEncoder stages (128 < C <= 512)
+ * The layer tail and its full-resolution backward for stage widths above 128 (model.depth > 32: the reference's
+ * h3_wider_cnn control runs depth 77, stages 154 / 231 / 308 / 308): sd_pool_rms_fwd / sd_pool_rms_bwd and their
+ * FiLM forms with one wave (64 lanes x 4 or 8 channels) per pooled pixel, any C in 129 .. SD_POOL_WIDE_MAX (odd
+ * counts included). Same arguments, same semantics (NaN-propagating argmax, nchw_flat, the odd-H / odd-W edge zeroing,
+ * rstd per pooled pixel), no atomics, fixed summation order. SD_ESHAPE (nothing launched, no pointer read) for every
+ * other C: the narrow entries above keep C <= 128.
+ * dw_partial >= (sd_pool_rms_wide_bwd_blocks + sd_colsum_chunks(sd_pool_rms_wide_bwd_blocks)) * C floats;
+ * film_partial >= sd_film_grad_wide_floats floats. */
+#define SD_POOL_WIDE_MAX 512
+int sd_pool_rms_wide_fwd(const float* x, const float* w, float* pooled, uint8_t* amax, float* y, float* rstd, int Nb,
+                         int H, int W, int C, float eps, int nchw_flat, sd_stream stream);
+int sd_pool_rms_wide_fwd_film(const float* x, const float* w, const float* gamma, const float* beta, int ipc,
+                              float* pooled, uint8_t* amax, float* y, float* rstd, int Nb, int H, int W, int C,
+                              float eps, int nchw_flat, sd_stream stream);
+int sd_pool_rms_wide_bwd_blocks(int Nb, int H, int W);
+int sd_film_grad_wide_floats(int Nb, int ipc, int H, int W, int C);
+int sd_pool_rms_wide_bwd(const float* pooled, const uint8_t* amax, const float* w, const float* rstd, const float* dy,
+                         float* dx, float* dw, float* dw_partial, int Nb, int H, int W, int C, int nchw_flat,
+                         int accumulate_dw, sd_stream stream);
+int sd_pool_rms_wide_bwd_film(const float* pooled, const uint8_t* amax, const float* w, const float* gamma,
+                              const float* beta, int ipc, const float* rstd, const float* dy, float* dx, float* dw,
+                              float* dw_partial, float* dgamma, float* dbeta, float* film_partial, int Nb, int H,
+                              int W, int C, int nchw_flat, int accumulate_dw, sd_stream stream);
+/* The two backward contractions of a stride-1 convolution with a channel count above 128 on the split-bf16 path
+ * (gemm3_core.h: operands split to (hi, lo) bf16 when staged, three bf16 MFMAs per product, f32 accumulation), as
+ * implicit GEMMs tiled 128 x 64 over M and N; M, N and K tails masked, so any channel counts and any K.
+ * dgrad: arguments as sd_conv2d_dgrad_bf16x3 (Ci = dOut's channels, Co = dIn's, wflip from sd_conv_flip_weight).
+ * wgrad: [dW | db] (Co, kh*kw*Ci + 1) as sd_conv2d_wgrad with ups = 0; K (pixels) in `slabs` slabs summed in slab
+ * order (<= 0: the library's count), acc as there; workspace >= slabs * Co * (kh*kw*Ci + 1) floats, one slab included.
+ * _ok / _slabs: host-only, no pointer involved; 0 where max(Ci, Co) <= 128 or a size leaves the int range, and the
+ * entry then returns SD_ESHAPE with nothing launched. _slabs(request) is the count the entry will use. The bwd-weight
+ * also refuses Ci < SD_WIDE3_WGRAD_MIN_CI (a first stage's few input channels: the f32 tiles are faster there). */
+#define SD_WIDE3_WGRAD_MIN_CI 64
+int sd_conv2d_dgrad_wide3_ok(int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad);
+int sd_conv2d_dgrad_wide3(const float* dout, const float* wflip, float* din, int Nb, int Hs, int Ws, int Ci, int Co,
+                          int kh, int kw, int pad, sd_stream stream);
+int sd_conv2d_wgrad_wide3_slabs(int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int request);
+int sd_conv2d_wgrad_wide3(const float* in, const float* dout, float* dw_db, float* workspace, long ws_floats,
+                          int slabs, int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad,
+                          const sd_wgrad_acc* acc, sd_stream stream);
+
 /* ---------------------------------------------------------------- text-conditioned (multimodal) encoder
  * FiLM stage: y = silu(gamma[n / ipc][c] * rms(maxpool(conv))[c] + beta[n / ipc][c]); gamma / beta (Nb / ipc, C) f32,
  * ipc = images per context row (Nb % ipc == 0, else SD_EARG). The forwards are the plain stage's kernels instantiated

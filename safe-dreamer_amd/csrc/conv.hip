@@ -1273,6 +1273,233 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad3(GemmArgs g, Geom G, int lw
   epilogue16<BM, BN, 32, BN>(g, acc, bm0, 0, 0, 0);
 }
 
+// ---------------------------------------------------------------- wide stages (a channel count above 128)
+// The same two contractions tiled over N as well as M, for the shapes the kernels above refuse (Co <= 64 is baked into
+// them): any channel counts (154, 231: no multiple of 4), any K (25 * 154 = 3850: past the tap table, no multiple of
+// 32). 128 x 64 tiles, 4 waves along M, gemm3_mainloop; M, N and K tails masked by the loaders and by epilogue16.
+
+// A operand of the wide bwd-data: Im2colRows' rows and k order, but no division in the K loop. A thread's first k of a
+// tile is kbeg + 32 t + 4 (tid % 8) for all its rows, so its (ky, kx, c) is decoded once and stepped by 32 channels
+// per tile; inside a float4 the channel steps by one and wraps into the next tap. VEC: C % 4 == 0 and a 16-B aligned
+// base (the four k's share one tap). The main loop asks for the tiles in ascending order. ups = 0.
+template <int ROWS, bool VEC>
+struct Im2colRowsInc {
+  static constexpr int NV = (ROWS * BK / 4 + 255) / 256;
+  Geom G;
+  int pn[NV], py[NV], px[NV];
+  int kcur, c, ky, kx;
+  TileLoader<ROWS, true, false> st;  // only for store() (KCSplit reads st.r)
+  SD_DEV Im2colRowsInc(const Geom& g, int M, int row0, int kbeg) : G(g) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int i = threadIdx.x + v * 256;
+      const int m = row0 + i / (BK / 4);
+      pn[v] = -1;
+      if (i < ROWS * BK / 4 && m < M) {
+        const int hw = G.Hg * G.Wg;
+        pn[v] = m / hw;
+        const int rem = m - pn[v] * hw;
+        py[v] = rem / G.Wg;
+        px[v] = rem - py[v] * G.Wg;
+      }
+    }
+    kcur = kbeg + 4 * (threadIdx.x % (BK / 4));
+    const int t = kcur / G.C;
+    c = kcur - t * G.C;
+    ky = t / G.kw;
+    kx = t - ky * G.kw;
+  }
+  SD_DEV bool tap_base(int v, int ty, int tx, long& off) const {
+    const int yy = py[v] + ty - G.pad, xx = px[v] + tx - G.pad;
+    off = (((long)pn[v] * G.Hs + yy) * G.Ws + xx) * G.C;
+    return yy >= 0 && yy < G.Hg && xx >= 0 && xx < G.Wg;
+  }
+  SD_DEV void load(int k0, int kend) {
+    const int gk = k0 + 4 * (threadIdx.x % (BK / 4));
+    while (kcur < gk) {
+      kcur += BK;
+      c += BK;
+      while (c >= G.C) {
+        c -= G.C;
+        if (++kx == G.kw) { kx = 0; ++ky; }
+      }
+    }
+    // every load is issued unconditionally (a masked-off element reads in[0] and is dropped): a load under a branch
+    // makes hipcc wait for it at the merge, which serialises the tile's loads
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      f32x4 x = {0.f, 0.f, 0.f, 0.f};
+      const bool row = pn[v] >= 0 && gk < kend;
+      long off;
+      bool ok = tap_base(v, ky, kx, off) && row;
+      if (VEC) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(G.in + (ok ? off + c : 0));
+        if (ok) x = t;
+      } else {
+        int cc = c, ty = ky, tx = kx;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool okj = ok && gk + j < kend;
+          const float t = G.in[okj ? off + cc : 0];
+          x[j] = okj ? t : 0.f;
+          if (++cc == G.C) {
+            cc = 0;
+            if (++tx == G.kw) { tx = 0; ++ty; }
+            ok = tap_base(v, ty, tx, off) && row;
+          }
+        }
+      }
+      st.r[v] = x;
+    }
+  }
+};
+
+// B operand of the wide bwd-weight: Im2colCols' rows j = (ky, kx, ci) with the bias ones-row at j == J, k = pixel,
+// staged as split bf16. A thread keeps ONE row j for the whole K loop (tid % ROWS, decoded once) and loads four
+// consecutive pixels of it per slot: consecutive lanes read consecutive channels of one tap (coalesced), and the four
+// pixels are one k-run of the LDS row (one 8-B store per plane, where Im2colCols' layout would need eight 2-B ones).
+template <int ROWS>
+struct Im2colColsPix {
+  static_assert(256 % ROWS == 0, "one row per thread");
+  static constexpr int NV = ROWS * BK / 4 / 256;
+  Geom G;
+  int J, j, ky, kx, c;
+  f32x4 r[NV];
+  SD_DEV Im2colColsPix(const Geom& g, int J_, int row0) : G(g), J(J_) {
+    j = row0 + threadIdx.x % ROWS;
+    const int t = j / G.C;
+    c = j - t * G.C;
+    ky = t / G.kw;
+    kx = t - ky * G.kw;
+  }
+  SD_DEV void load(int k0, int kend) {
+    const int hw = G.Hg * G.Wg;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int m0 = k0 + 4 * ((threadIdx.x + v * 256) / ROWS);
+      f32x4 x = {0.f, 0.f, 0.f, 0.f};
+      // (m0 >= kend decodes to pixels past the batch: every element is masked; loads unconditional, as above)
+      int n = m0 / hw;
+      const int rem = m0 - n * hw;
+      int y = rem / G.Wg, xq = rem - y * G.Wg;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool live = m0 + e < kend;
+        const int yy = y + ky - G.pad, xx = xq + kx - G.pad;
+        const bool in = live && j < J && yy >= 0 && yy < G.Hg && xx >= 0 && xx < G.Wg;
+        const float t = G.in[in ? (((long)n * G.Hs + yy) * G.Ws + xx) * G.C + c : 0];
+        x[e] = in ? t : (live && j == J ? 1.f : 0.f);
+        if (++xq == G.Wg) {
+          xq = 0;
+          if (++y == G.Hg) { y = 0; ++n; }
+        }
+      }
+      r[v] = x;
+    }
+  }
+  SD_DEV void store(__bf16* lds) const {
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+      sdb::split_store(lds + (threadIdx.x % ROWS) * sdb::LROW + 4 * ((threadIdx.x + v * 256) / ROWS), r[v]);
+  }
+};
+
+// gemm3_core.h's two dense operands with every load issued unconditionally (masked-off elements read p[0])
+template <int ROWS, bool VEC>
+struct KC3U : sdb::KC3<ROWS, VEC> {
+  using B = sdb::KC3<ROWS, VEC>;
+  using B::B;
+  SD_DEV void load(int k0, int kend) {
+#pragma unroll
+    for (int v = 0; v < B::NV; ++v) {
+      const int i = threadIdx.x + v * 256;
+      const int row = i / (BK / 4), gk = k0 + 4 * (i % (BK / 4)), gr = this->row0 + row;
+      const bool ok = i < ROWS * BK / 4 && gr < this->nrows;
+      const long off = (long)gr * this->ld + gk;
+      f32x4 x = {0.f, 0.f, 0.f, 0.f};
+      if (VEC) {  // K % 4 == 0: the four k's are inside together
+        const bool okv = ok && gk < kend;
+        const f32x4 t = *reinterpret_cast<const f32x4*>(this->p + (okv ? off : 0));
+        if (okv) x = t;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool okj = ok && gk + j < kend;
+          const float t = this->p[okj ? off + j : 0];
+          x[j] = okj ? t : 0.f;
+        }
+      }
+      this->r[v] = x;
+    }
+  }
+};
+
+template <int ROWS, bool VEC>
+struct KM3U : sdb::KM3<ROWS, VEC> {
+  using B = sdb::KM3<ROWS, VEC>;
+  using B::B;
+  SD_DEV void load(int k0, int kend) {
+#pragma unroll
+    for (int v = 0; v < B::NV; ++v) {
+      const int i = threadIdx.x + v * 256;
+      const int rq = i % (ROWS / 4), kq = i / (ROWS / 4);
+      const int gr = this->row0 + 4 * rq;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const int gk = k0 + 4 * kq + kk;
+        const bool ok = i < B::NBLK && gk < kend;
+        const long off = (long)gk * this->ld + gr;
+        f32x4 x = {0.f, 0.f, 0.f, 0.f};
+        if (VEC) {  // nrows % 4 == 0: the four rows are inside together
+          const bool okv = ok && gr < this->nrows;
+          const f32x4 t = *reinterpret_cast<const f32x4*>(this->p + (okv ? off : 0));
+          if (okv) x = t;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const bool okj = ok && gr + j < this->nrows;
+            const float t = this->p[okj ? off + j : 0];
+            x[j] = okj ? t : 0.f;
+          }
+        }
+        this->r[v][kk] = x;
+      }
+    }
+  }
+};
+
+constexpr int WIDE_BM = 128, WIDE_BN = 64;
+
+// bwd-data: M = pixels, N = dIn's channels in 64-wide tiles, K = kh*kw*C(dOut). Workgroup b: N tile b % ntn of M tile
+// b / ntn, so the N tiles of one pixel block run side by side and share its dOut rows in L2.
+template <bool VA, bool VB>
+__global__ __launch_bounds__(256, 2) void conv_dgrad_wide3(GemmArgs g, Geom G, int ntn) {
+  constexpr int BM = WIDE_BM, BN = WIDE_BN;
+  const int bn0 = (blockIdx.x % ntn) * BN, bm0 = (blockIdx.x / ntn) * BM;
+  Im2colRowsInc<BM, VA> la0(G, g.M, bm0, 0);
+  KCSplit<Im2colRowsInc<BM, VA>, BM> la(la0);
+  KC3U<BN, VB> lb(g.B, g.ldb, g.N, bn0);
+  f32x4 acc[2][BN / 16];
+  sdb::gemm3_mainloop<BM, BN, 32, BN>(la, lb, 0, g.K, acc);
+  epilogue16<BM, BN, 32, BN>(g, acc, bm0, bn0, 0, 0);
+}
+
+// bwd-weight: M = Co in 128-row tiles, N = j (+ the bias column) in 64-wide tiles, K = pixels, split into gridDim.y
+// slabs of g.kchunk pixels; every slab goes to the workspace (slab_reduce sums them, one slab included).
+template <bool VA>
+__global__ __launch_bounds__(256, 2) void conv_wgrad_wide3(GemmArgs g, Geom G, int J, int ntn) {
+  constexpr int BM = WIDE_BM, BN = WIDE_BN;
+  const int bn0 = (blockIdx.x % ntn) * BN, bm0 = (blockIdx.x / ntn) * BM;
+  const int split = blockIdx.y;
+  const int kbeg = split * g.kchunk;
+  const int kend = min(g.K, kbeg + g.kchunk);
+  KM3U<BM, VA> la(g.A, g.lda, g.M, bm0);
+  Im2colColsPix<BN> lb(G, J, bn0);
+  f32x4 acc[2][BN / 16];
+  sdb::gemm3_mainloop<BM, BN, 32, BN>(la, lb, kbeg, kend, acc);
+  epilogue16<BM, BN, 32, BN>(g, acc, bm0, bn0, 0, split);
+}
+
 // bwd-data as a DIRECT convolution on split-bf16 MFMAs: conv_dgrad3's contraction (dIn = conv_same(dOut, flipped W),
 // K = (ky, kx, c) with c contiguous), but each workgroup stages its dOut patch (R image rows + the kh-1 / kw-1 halo,
 // zero outside the image) ONCE in LDS, split to (hi, lo) bf16 planes on the way in, and every tap reads its shifted
@@ -2624,6 +2851,184 @@ extern "C" int sd_conv2d_dgrad_pool(const float* dpool, const uint8_t* amax, con
   if (Nb <= 0) return SD_OK;
   if (!dpool || !amax || !w || !din) return SD_EARG;
   conv_dgrad_pool_k<<<Nb * sd_cdiv(H, DP_TH), 256, 0, (hipStream_t)stream_>>>(dpool, amax, w, din, H);
+  SD_LAUNCH_CHECK();
+  return SD_OK;
+}
+
+// ---------------------------------------------------------------- wide stages: row kernels, 128 < C <= 512
+// pool_rms_fwd / pool_rms_bwd / film_grad_partial with a whole wave per pooled pixel (T = 64, 4 or 8 channels per
+// lane): the same code line for line, ss and dot summed over the 64 lanes, 4 pixels per workgroup step. The narrow
+// entries keep refusing C > 128; these refuse everything else, before any launch.
+static bool wide_rows(int C) { return C > 128 && C <= SD_POOL_WIDE_MAX; }
+
+#define SD_WIDE_SWITCH(LAUNCH)                \
+  if (vpt_for(C, 64) <= 4) { LAUNCH(4); }     \
+  else { LAUNCH(8); }
+
+template <class NW>
+static int pool_rms_wide_fwd_impl(const float* x, NW w, float* pooled, uint8_t* amax, float* y, float* rstd, int Nb,
+                                  int H, int W, int C, float eps, int nchw_flat, hipStream_t s) {
+  const long P = (long)Nb * (H / 2) * (W / 2);
+  if (P <= 0) return SD_OK;
+  if ((P + 3) / 4 > 0x7fffffffL) return SD_ESHAPE;
+  const int grid = (int)((P + 3) / 4);
+#define SD_L(V) pool_rms_fwd<64, V, NW><<<grid, 256, 0, s>>>(x, w, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat)
+  SD_WIDE_SWITCH(SD_L)
+#undef SD_L
+  SD_LAUNCH_CHECK();
+  return SD_OK;
+}
+
+extern "C" int sd_pool_rms_wide_fwd(const float* x, const float* w, float* pooled, uint8_t* amax, float* y,
+                                    float* rstd, int Nb, int H, int W, int C, float eps, int nchw_flat,
+                                    sd_stream stream_) {
+  if (!wide_rows(C)) return SD_ESHAPE;
+  return pool_rms_wide_fwd_impl<const float*>(x, w, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat,
+                                              (hipStream_t)stream_);
+}
+
+extern "C" int sd_pool_rms_wide_fwd_film(const float* x, const float* w, const float* gamma, const float* beta,
+                                         int ipc, float* pooled, uint8_t* amax, float* y, float* rstd, int Nb, int H,
+                                         int W, int C, float eps, int nchw_flat, sd_stream stream_) {
+  if (!wide_rows(C)) return SD_ESHAPE;
+  if (!gamma || !beta || ipc <= 0 || Nb % ipc) return SD_EARG;
+  return pool_rms_wide_fwd_impl(x, FilmNW{w, gamma, beta, ipc}, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat,
+                                (hipStream_t)stream_);
+}
+
+extern "C" int sd_pool_rms_wide_bwd_blocks(int Nb, int H, int W) {
+  const long P = (long)Nb * (H / 2) * (W / 2);
+  const long b = (P + 3) / 4;
+  return (int)(b < 2048 ? (b > 0 ? b : 1) : 2048);
+}
+
+static int film_grad_wide_blocks(int ipc, int H, int W) {
+  const long b = ((long)ipc * (H / 2) * (W / 2) + 3) / 4;
+  return (int)(b < 64 ? (b > 0 ? b : 1) : 64);
+}
+
+extern "C" int sd_film_grad_wide_floats(int Nb, int ipc, int H, int W, int C) {
+  if (ipc <= 0) return 0;
+  return (Nb / ipc) * film_grad_wide_blocks(ipc, H, W) * 2 * C;
+}
+
+extern "C" int sd_pool_rms_wide_bwd(const float* pooled, const uint8_t* amax, const float* w, const float* rstd,
+                                    const float* dy, float* dx, float* dw, float* dw_partial, int Nb, int H, int W,
+                                    int C, int nchw_flat, int accumulate_dw, sd_stream stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  if (!wide_rows(C)) return SD_ESHAPE;
+  const int grid = sd_pool_rms_wide_bwd_blocks(Nb, H, W);
+  if (pool_rms_bwd_empty(dx, Nb, H, W, C, s) != SD_OK) return SD_EARG;
+#define SD_L(V) \
+  pool_rms_bwd<64, V><<<grid, 256, 0, s>>>(pooled, amax, w, rstd, dy, dx, dw_partial, Nb, H, W, C, nchw_flat)
+  SD_WIDE_SWITCH(SD_L)
+#undef SD_L
+  SD_LAUNCH_CHECK();
+  return sd_colsum_ws(dw_partial, dw, grid, C, C, accumulate_dw, dw_partial + (long)grid * C, stream_);
+}
+
+extern "C" int sd_pool_rms_wide_bwd_film(const float* pooled, const uint8_t* amax, const float* w, const float* gamma,
+                                         const float* beta, int ipc, const float* rstd, const float* dy, float* dx,
+                                         float* dw, float* dw_partial, float* dgamma, float* dbeta,
+                                         float* film_partial, int Nb, int H, int W, int C, int nchw_flat,
+                                         int accumulate_dw, sd_stream stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  if (!wide_rows(C)) return SD_ESHAPE;
+  if (!gamma || !beta || !dgamma || !dbeta || !film_partial || ipc <= 0 || Nb % ipc) return SD_EARG;
+  if (Nb <= 0) return SD_OK;
+  const int grid = sd_pool_rms_wide_bwd_blocks(Nb, H, W);
+  const FilmNW f{w, gamma, beta, ipc};
+  const int rows = Nb / ipc, nblk = film_grad_wide_blocks(ipc, H, W);
+  if (pool_rms_bwd_empty(dx, Nb, H, W, C, s) != SD_OK) return SD_EARG;
+  const dim3 fgrid(nblk, rows);
+#define SD_L(V)                                                                                                     \
+  pool_rms_bwd<64, V, false, FilmNW><<<grid, 256, 0, s>>>(pooled, amax, f, rstd, dy, dx, dw_partial, Nb, H, W, C,   \
+                                                          nchw_flat);                                               \
+  SD_LAUNCH_CHECK();                                                                                                \
+  film_grad_partial<64, V><<<fgrid, 256, 0, s>>>(pooled, f, rstd, dy, film_partial, H / 2, W / 2, C, nchw_flat)
+  SD_WIDE_SWITCH(SD_L)
+#undef SD_L
+  SD_LAUNCH_CHECK();
+  film_grad_final<<<sd_cdiv((long)rows * C, 256), 256, 0, s>>>(film_partial, w, dgamma, dbeta, rows, nblk, C);
+  SD_LAUNCH_CHECK();
+  return sd_colsum_ws(dw_partial, dw, grid, C, C, accumulate_dw, dw_partial + (long)grid * C, stream_);
+}
+#undef SD_WIDE_SWITCH
+
+// ---------------------------------------------------------------- wide stages: split-bf16 backward contractions
+// Shapes with a channel count above 128 (every older split-bf16 arm refuses them), pixel and tile counts in int range.
+static bool wide3_shape(int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw) {
+  if (Nb <= 0 || Hs <= 0 || Ws <= 0 || Ci <= 0 || Co <= 0 || kh <= 0 || kw <= 0) return false;
+  if (Ci <= 128 && Co <= 128) return false;
+  const long M = (long)Nb * Hs * Ws, K = (long)kh * kw * Ci + 1;
+  return M < (1L << 30) && K < (1L << 24) && sd_cdiv(M, WIDE_BM) * sd_cdiv((long)Co, WIDE_BN) < (1L << 30);
+}
+
+// dgrad arguments as sd_conv2d_dgrad_bf16x3: Ci = dOut's channels, Co = dIn's
+extern "C" int sd_conv2d_dgrad_wide3_ok(int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int pad) {
+  return wide3_shape(Nb, Hs, Ws, Ci, Co, kh, kw) && pad >= 0 && pad < kh && pad < kw;
+}
+
+extern "C" int sd_conv2d_dgrad_wide3(const float* dout, const float* wflip, float* din, int Nb, int Hs, int Ws,
+                                     int Ci, int Co, int kh, int kw, int pad, sd_stream stream_) {
+  if (!sd_conv2d_dgrad_wide3_ok(Nb, Hs, Ws, Ci, Co, kh, kw, pad)) return SD_ESHAPE;
+  if (!dout || !wflip || !din) return SD_EARG;
+  Geom G{dout, Nb, Hs, Ws, Ci, Hs, Ws, kh, kw, pad, 0};
+  GemmArgs g{};
+  g.B = wflip; g.C = din; g.ldb = (long)kh * kw * Ci; g.ldc = Co;
+  g.M = Nb * Hs * Ws; g.N = Co; g.K = kh * kw * Ci; g.batch = 1; g.ksplit = 1; g.kchunk = g.K;
+  g.alpha = 1.f; g.beta = 0.f;
+  const bool va = Ci % 4 == 0 && aligned16(dout), vb = g.K % 4 == 0 && aligned16(wflip);
+  const int ntn = sd_cdiv(Co, WIDE_BN);
+  const int grid = ntn * sd_cdiv(g.M, WIDE_BM);
+  with_bools([&](auto VA, auto VB) {
+    conv_dgrad_wide3<VA(), VB()><<<grid, 256, 0, (hipStream_t)stream_>>>(g, G, ntn);
+  }, va, vb);
+  SD_LAUNCH_CHECK();
+  return SD_OK;
+}
+
+// slabs of the wide bwd-weight: `request` > 0 as asked (at most one per 32-pixel k tile), else enough workgroups for
+// about four per CU, no slab under 8 k tiles, at most 64; 0: the shape is not the wide arm's
+extern "C" int sd_conv2d_wgrad_wide3_slabs(int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw, int request) {
+  // Ci < 64 (a first stage: the 4-channel padded image): a wave's 64 im2col rows scatter over 16 taps and the f32
+  // tiles are faster (measured, profiles/wide_encoder.md): not routed
+  if (!wide3_shape(Nb, Hs, Ws, Ci, Co, kh, kw) || Ci < SD_WIDE3_WGRAD_MIN_CI) return 0;
+  const long ktiles = sd_cdiv((long)Nb * Hs * Ws, (long)BK);
+  long s = request;
+  if (request <= 0) {
+    const long tiles = sd_cdiv((long)Co, WIDE_BM) * sd_cdiv((long)kh * kw * Ci + 1, WIDE_BN);
+    s = sd_cdiv(1024L, tiles);
+    if (s > ktiles / 8) s = ktiles / 8;
+    if (s > 64) s = 64;
+  }
+  if (s > ktiles) s = ktiles;
+  return (int)(s < 1 ? 1 : s);
+}
+
+extern "C" int sd_conv2d_wgrad_wide3(const float* in, const float* dout, float* dw_db, float* workspace,
+                                     long ws_floats, int slabs, int Nb, int Hs, int Ws, int Ci, int Co, int kh, int kw,
+                                     int pad, const sd_wgrad_acc* acc_p, sd_stream stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  const int ks = sd_conv2d_wgrad_wide3_slabs(Nb, Hs, Ws, Ci, Co, kh, kw, slabs);
+  if (ks <= 0 || pad < 0 || pad >= kh || pad >= kw) return SD_ESHAPE;
+  sd_wgrad_acc acc;
+  if (!wgrad_acc_arg(acc_p, Ci, acc) || !in || !dout || !dw_db || !workspace) return SD_EARG;
+  const int J = kh * kw * Ci;
+  if (ws_floats < (long)ks * Co * (J + 1)) return SD_EARG;
+  Geom G{in, Nb, Hs, Ws, Ci, Hs, Ws, kh, kw, pad, 0};
+  GemmArgs g{};
+  g.A = dout; g.lda = Co; g.C = workspace; g.ldc = J + 1; g.ws = workspace;
+  g.M = Co; g.N = J + 1; g.K = Nb * Hs * Ws; g.batch = 1; g.ksplit = ks;
+  g.kchunk = (int)(sd_cdiv(sd_cdiv((long)g.K, (long)ks), (long)BK) * BK);
+  g.alpha = 1.f; g.beta = 0.f;
+  const bool va = Co % 4 == 0 && aligned16(dout);
+  const int ntn = sd_cdiv(g.N, WIDE_BN);
+  const dim3 grid(ntn * sd_cdiv(Co, WIDE_BM), ks);
+  with_bools([&](auto VA) { conv_wgrad_wide3<VA()><<<grid, 256, 0, s>>>(g, G, J, ntn); }, va);
+  SD_LAUNCH_CHECK();
+  const long total = (long)Co * (J + 1);
+  slab_reduce<<<(int)((total + 63) / 64), 256, 0, s>>>(workspace, ks, total, dw_db, acc, J, Ci);
   SD_LAUNCH_CHECK();
   return SD_OK;
 }

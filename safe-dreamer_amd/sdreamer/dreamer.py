@@ -30,8 +30,8 @@ from . import _native as nat
 from . import kernels as K
 from . import ops
 from . import parallel
-from .networks import (Linear, MLPHead, MultiDecoder, MultiEncoder, Projector, ReturnEMA, heads_nograd,
-                       pair_forward_from_first)
+from .networks import (Linear, MLPHead, MultiDecoder, MultiEncoder, Projector, ReturnEMA, check_stage_widths,
+                       heads_nograd, pair_forward_from_first)
 from .optim import LaProp, WarmupSchedule
 from .rssm import RSSM, STREAM_ACT, STREAM_IMG, STREAM_OBS_AUG, STREAM_POLICY, STREAM_POLICY_ACT
 
@@ -82,6 +82,11 @@ class Dreamer(nn.Module):
         if self.device.type != "cuda":
             raise RuntimeError("sdreamer.Dreamer runs on a HIP device only (config.device must be cuda:N)")
         self.config = config
+        if any(len(tuple(v.shape)) == 3 for v in obs_space.spaces.values()):
+            # an image observation gets a conv encoder: its widths are refused here, before anything is allocated on
+            # the device (the encoder's constructor checks them again for every other caller)
+            cnn = config.encoder.cnn
+            check_stage_widths([int(cnn.depth) * int(m) for m in list(cnn.mults)])
         self.act_entropy = float(config.act_entropy)
         self.kl_free = float(config.kl_free)
         self.imag_horizon = int(config.imag_horizon)

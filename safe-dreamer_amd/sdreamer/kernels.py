@@ -635,7 +635,25 @@ def conv2d_dgrad(dout, w, pad=None, fast=True, direct=True):
         if nat.call_shaped("sd_conv2d_dgrad_bf16x3", p(_c(dout)), p(wf), p(din), Nb, H, W, Co, Ci, kh, kw, pad,
                            stream()):
             return din
+        if conv2d_dgrad_wide_takes(Nb, H, W, Co, Ci, kh, kw, pad):  # a channel count above 128: the N-tiled arm
+            nat.call("sd_conv2d_dgrad_wide3", p(_c(dout)), p(wf), p(din), Nb, H, W, Co, Ci, kh, kw, pad, stream())
+            return din
     return conv2d_fwd(dout, wf, None, pad=pad)
+
+
+def conv2d_dgrad_wide_takes(Nb, H, W, Co, Ci, kh, kw, pad):
+    """True where conv2d_dgrad's last split-bf16 arm (sd_conv2d_dgrad_wide3) takes the shape: max(Ci, Co) > 128.
+    Co = dOut's channels, Ci = dIn's, as the weight (Co, kh, kw, Ci) names them."""
+    return max(Ci, Co) > WIDE_ROWS_MIN and nat.fns["sd_conv2d_dgrad_wide3_ok"](Nb, H, W, Co, Ci, kh, kw, pad) > 0
+
+
+def conv2d_wgrad_wide_slabs(Nb, H, W, Ci, Co, kh, kw, request=0):
+    """Slab count of conv2d_wgrad's last split-bf16 arm (sd_conv2d_wgrad_wide3) for this request, 0 where it does not
+    take the shape: both channel counts <= 128, or fewer than 64 input channels (a first stage: the f32 tiles are
+    faster there, profiles/wide_encoder.md)."""
+    if max(Ci, Co) <= WIDE_ROWS_MIN:
+        return 0
+    return nat.fns["sd_conv2d_wgrad_wide3_slabs"](Nb, H, W, Ci, Co, kh, kw, int(request))
 
 
 def _wgrad_acc(acc):
@@ -664,10 +682,11 @@ def _wgrad_call(name, ks, shape, acc, ptrs, tail, shaped=False):
     return None if acc is not None else out
 
 
-def conv2d_wgrad(x, dout, kh, kw, ups=0, pad=None, fast=True, acc=None):
+def conv2d_wgrad(x, dout, kh, kw, ups=0, pad=None, fast=True, acc=None, wide_slabs=0):
     """returns (Co, kh*kw*Ci + 1) = [dW | db]. fast: split-bf16 direct kernel (sd_conv2d_wgrad_bf16x3) where eligible
-    (Ci >= 16; the 4-channel first layer keeps the f32 direct kernel). acc = (dw, db, ci_w): the result is added into
-    those parameter gradients by the launch's own reduction instead (returns None)."""
+    (Ci >= 16; the 4-channel first layer keeps the f32 direct kernel), then, with a channel count above 128, the
+    N-tiled split-bf16 implicit GEMM (sd_conv2d_wgrad_wide3; wide_slabs > 0 fixes its slab count). acc = (dw, db,
+    ci_w): the result is added into those parameter gradients by the launch's own reduction instead (returns None)."""
     Nb, H, W, Ci = x.shape
     Co = dout.shape[-1]
     pad = (kh - 1) // 2 if pad is None else pad
@@ -680,6 +699,9 @@ def conv2d_wgrad(x, dout, kh, kw, ups=0, pad=None, fast=True, acc=None):
                               shaped=True)
             if out is not False:
                 return out
+        ks = conv2d_wgrad_wide_slabs(Nb, H, W, Ci, Co, kh, kw, wide_slabs) if ups == 0 else 0
+        if ks > 0:
+            return _wgrad_call("sd_conv2d_wgrad_wide3", ks, shape, acc, ptrs, (ks, Nb, H, W, Ci, Co, kh, kw, pad))
     pixels = dout.numel() // Co
     ks = max(1, min(256, pixels // 4096))
     tiles = -(-Co // 64) * -(-(J + 1) // 64)
@@ -1055,16 +1077,18 @@ def conv2d_fwd_pool(x, w, b, nw, nchw_flat=False, film=None):
     return (y, pooled, amax, rstd) if ok else None
 
 
-def _pool_rms_bwd(stem, out_shape, pooled, amax, w, rstd, dy, H, W, dw, nchw_flat, film):
-    """pool_rms_bwd / pool_rms_bwd_compact: entry `stem` (`stem`_film with film) writes the gradient of out_shape"""
+def _pool_rms_bwd(stem, out_shape, pooled, amax, w, rstd, dy, H, W, dw, nchw_flat, film, wide=""):
+    """pool_rms_bwd / pool_rms_bwd_compact / pool_rms_wide_bwd: entry `stem` (`stem`_film with film) writes the
+    gradient of out_shape; wide = "_wide": the wide rows' block and FiLM-partial counts"""
     Nb, Ho, Wo, C = pooled.shape
     d = torch.empty(out_shape, dtype=torch.float32, device=pooled.device)
-    nb = nat.fns["sd_pool_rms_bwd_blocks"](Nb, H, W)
+    nb = nat.fns[f"sd_pool_rms{wide}_bwd_blocks"](Nb, H, W)
     part = torch.empty((nb + nat.fns["sd_colsum_chunks"](nb)) * C, dtype=torch.float32, device=pooled.device)
     if film is not None:
         gamma, beta, ipc = _film_args(film, Nb, C)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        fpart = torch.empty(nat.fns["sd_film_grad_floats"](Nb, ipc, H, W, C), dtype=torch.float32, device=pooled.device)
+        fpart = torch.empty(nat.fns[f"sd_film_grad{wide}_floats"](Nb, ipc, H, W, C), dtype=torch.float32,
+                            device=pooled.device)
         nat.call(stem + "_film", p(pooled), p(amax), p(w), p(gamma), p(beta), ipc, p(rstd), p(_c(dy)), p(d), p(dw),
                  p(part), p(dgamma), p(dbeta), p(fpart), Nb, H, W, C, int(nchw_flat), 1, stream())
         return d, dgamma, dbeta
@@ -1085,6 +1109,31 @@ def pool_rms_bwd(pooled, amax, w, rstd, dy, H, W, dw, nchw_flat=False, film=None
     """film = (gamma, beta): returns (dx, dgamma, dbeta)"""
     Nb, Ho, Wo, C = pooled.shape
     return _pool_rms_bwd("sd_pool_rms_bwd", (Nb, H, W, C), pooled, amax, w, rstd, dy, H, W, dw, nchw_flat, film)
+
+
+# Stage widths above WIDE_ROWS_MIN run the wide row kernels (a wave per pooled pixel), up to WIDE_ROWS_MAX channels
+WIDE_ROWS_MIN = 128
+WIDE_ROWS_MAX = nat._define(nat.HEADER, "SD_POOL_WIDE_MAX")
+
+
+def pool_rms_wide_fwd(x, w, nchw_flat=False, film=None):
+    """pool_rms_fwd for WIDE_ROWS_MIN < C <= WIDE_ROWS_MAX (sd_pool_rms_wide_fwd[_film]): same outputs, same meaning"""
+    Nb, H, W, C = x.shape
+    y, pooled, amax, rstd = _stage_outputs(Nb, H, W, C, x.device)
+    sfx, fa = "", ()
+    if film is not None:
+        gamma, beta, ipc = _film_args(film, Nb, C)
+        sfx, fa = "_film", (p(gamma), p(beta), ipc)
+    nat.call("sd_pool_rms_wide_fwd" + sfx, p(_c(x)), p(w), *fa, p(pooled), p(amax), p(y), p(rstd), Nb, H, W, C, EPS,
+             int(nchw_flat), stream())
+    return y, pooled, amax, rstd
+
+
+def pool_rms_wide_bwd(pooled, amax, w, rstd, dy, H, W, dw, nchw_flat=False, film=None):
+    """pool_rms_bwd for WIDE_ROWS_MIN < C <= WIDE_ROWS_MAX (sd_pool_rms_wide_bwd[_film]); film: (dx, dgamma, dbeta)"""
+    Nb, Ho, Wo, C = pooled.shape
+    return _pool_rms_bwd("sd_pool_rms_wide_bwd", (Nb, H, W, C), pooled, amax, w, rstd, dy, H, W, dw, nchw_flat, film,
+                         wide="_wide")
 
 
 # ------------------------------------------------------------------------------------------------- text conditioning

@@ -25,7 +25,7 @@ from torch import nn
 
 from . import kernels as K
 from . import ops
-from .networks import Act, Conv2d, ConvEncoder, Linear, RMSNorm, run_conv_stages
+from .networks import Act, Conv2d, ConvEncoder, Linear, RMSNorm, check_stage_widths, run_conv_stages
 
 TEXT_RESAMPLE_INTERVAL = 64  # training forwards between two text draws (encoder.py:121)
 
@@ -76,6 +76,7 @@ class FiLMConvEncoder(nn.Module):
         super().__init__()
         h, w, ch = input_shape
         self.depths = tuple(int(config.depth) * int(m) for m in list(config.mults))
+        check_stage_widths(self.depths)
         self.k = int(config.kernel_size)
         if not bool(config.norm):
             raise NotImplementedError("norm=False encoder")

@@ -325,6 +325,14 @@ def run_conv_stages(x, stages, split=None, pad_shift=None, ctx=None):
     return x
 
 
+def check_stage_widths(depths):
+    """A conv encoder's stage widths against the row kernels' limit, at construction (not a NativeError mid-update)"""
+    if max(depths) > K.WIDE_ROWS_MAX:
+        raise NotImplementedError(f"conv encoder stage widths {tuple(depths)}: the pool / RMSNorm / SiLU kernels hold "
+                                  f"at most {K.WIDE_ROWS_MAX} channels (model.depth * max(mults) <= "
+                                  f"{K.WIDE_ROWS_MAX})")
+
+
 class ConvEncoder(nn.Module):
     """networks.py:192-234. Input NHWC float in [0, 1] (B*T, 64, 64, 3); output (B*T, C*h*w) in NCHW flatten order."""
 
@@ -332,6 +340,7 @@ class ConvEncoder(nn.Module):
         super().__init__()
         h, w, ch = input_shape
         self.depths = tuple(int(config.depth) * int(m) for m in list(config.mults))
+        check_stage_widths(self.depths)
         self.k = int(config.kernel_size)
         if not bool(config.norm):
             raise NotImplementedError("norm=False encoder")

@@ -354,9 +354,16 @@ def _stage_input(x, w, pad_shift):
     return x, (w if x.shape[-1] == w.shape[-1] else _pad_last(w, x.shape[-1]))
 
 
+def _stage_wide(w):
+    """The one place a stage is sent to the wide row kernels (k.pool_rms_wide_fwd / k.pool_rms_wide_bwd): more output
+    channels than the narrow ones hold. No fused forward and no pooled-gradient route exists at these widths."""
+    return w.shape[0] > k.WIDE_ROWS_MIN
+
+
 def _stage_route(need_dx, x, w):
     """The one place a stage's backward route is chosen, for the conv input x (after _stage_input) and the weight w as
-    the module holds it: "first", "x3" or "full".
+    the module holds it: "first", "x3", "full" or "wide".
+    wide: _stage_wide(w). The full route on the wide row kernel; k.conv2d_wgrad / k.conv2d_dgrad pick their wide arms.
     first: the first stage. Its f32 / split-bf16 pooled bwd-weight (k.conv2d_wgrad_pool) takes the shape, and the input
     gradient is not wanted or x is channel-padded and k.conv2d_dgrad_pool takes it: both expand the pooled gradient +
     argmax themselves.
@@ -365,6 +372,8 @@ def _stage_route(need_dx, x, w):
     full: through the full-resolution conv gradient (3/4 zeros), which the other two never write or read."""
     Nb, H, W, Cx = x.shape
     Co, kh, kw, Ci = w.shape
+    if _stage_wide(w):
+        return "wide"
     if not POOL_COMPACT:
         return "full"
     if k.conv2d_wgrad_pool_slabs(x, Co, kh, kw) > 0 and (
@@ -427,10 +436,13 @@ class ConvPoolNormFn(torch.autograd.Function):
         ctx.raw_c = x.shape[-1] if pad_shift is not None else None
         x, wk = _stage_input(x, w, pad_shift)
         film = None if gamma is None else (gamma.contiguous(), beta.contiguous())
-        fused = k.conv2d_fwd_pool(x.contiguous(), wk, b, nw, nchw_flat=nchw_flat, film=film) if FUSED_POOL else None
+        wide = _stage_wide(w)
+        fused = None
+        if FUSED_POOL and not wide:
+            fused = k.conv2d_fwd_pool(x.contiguous(), wk, b, nw, nchw_flat=nchw_flat, film=film)
         if fused is None:
             conv = k.conv2d_fwd(x.contiguous(), wk, b)
-            fused = k.pool_rms_fwd(conv, nw, nchw_flat=nchw_flat, film=film)
+            fused = (k.pool_rms_wide_fwd if wide else k.pool_rms_fwd)(conv, nw, nchw_flat=nchw_flat, film=film)
             del conv
         y, pooled, amax, rstd = fused
         ctx.save_for_backward(x, w, b, nw, pooled, amax, rstd, *(film or ()))
@@ -448,7 +460,11 @@ class ConvPoolNormFn(torch.autograd.Function):
         need_dx = ctx.needs_input_grad[0]
         acc = (grad_buf(w), grad_buf(b), Ci)  # the bwd-weight launches add into the gradients themselves
         route = _stage_route(need_dx, x, w)
-        if route == "full":
+        if route == "wide":
+            d = k.pool_rms_wide_bwd(pooled, amax, nw, rstd, dy.contiguous(), H, W, grad_buf(nw),
+                                    nchw_flat=ctx.nchw_flat, film=film)
+            route = "full"  # from here on the full-resolution conv gradient's route
+        elif route == "full":
             d = k.pool_rms_bwd(pooled, amax, nw, rstd, dy.contiguous(), H, W, grad_buf(nw), nchw_flat=ctx.nchw_flat,
                                film=film)
         else:
