@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define SD_DEV __device__ __forceinline__
 
 // status codes returned across the C ABI (0 = ok, >0 = hipError_t, <0 = argument errors)
@@ -95,6 +97,12 @@ SD_DEV float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x))
 SD_DEV float siluf_(float x) { return x * __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
 static inline int sd_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// run-time int -> template argument (host launchers)
+template <int... Vs, class F>
+void with_int(int v, F&& f) {  // f(std::integral_constant<int, V>) for the V of the list that equals v
+  ((v == Vs ? f(std::integral_constant<int, Vs>{}) : void()), ...);
+}
 
 // Phase timestamps (measurement build, -DSD_SCAN_TRACE; scan.hip and img.hip kernels): thread 0 of every workgroup keeps entry / operands staged /
 // contraction reduced / exit (s_memrealtime, 100 MHz) and stores them at exit into trace[slot][workgroup][4].

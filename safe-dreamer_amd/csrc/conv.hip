@@ -1,5 +1,6 @@
-// Channels-last (NHWC) convolution as implicit GEMM on the shared MFMA core, plus the fused pooling/norm epilogue
-// kernels of the conv encoder/decoder.
+// Channels-last (NHWC) convolution as implicit GEMM on the shared MFMA core, plus the conv kernels of the conv
+// encoder/decoder with the pooling/norm stage fused into their epilogue. The stage's stand-alone row kernels
+// (max-pool + RMSNorm + SiLU forward and backward, FiLM gradients) and their entries are in poolnorm.hip.
 //
 // Reference: Conv2dSamePad (networks.py:59-85; stride 1, TF-SAME padding), ConvEncoder layers
 // [conv -> MaxPool2d(2) -> RMSNorm2D -> SiLU] (networks.py:192-234), ConvDecoder layers
@@ -16,10 +17,7 @@
 #include "gemm6_core.h"
 #include "gemm_core.h"
 #include "sdhip.h"
-
-extern "C" int sd_colsum(const float* in, float* out, int R, int N, long ld, int accumulate, sd_stream s);
-extern "C" int sd_colsum_ws(const float* in, float* out, int R, int N, long ld, int accumulate, float* workspace,
-                            sd_stream s);
+#include "stage_core.h"
 
 namespace {
 using namespace sdg;
@@ -274,20 +272,7 @@ struct EpiPre {
   float bias[BN / 16];
   float nw[BN / 8];
 };
-// FiLM stage (multimodal encoder): y = silu(gamma[n / ipc][c] * norm + beta[n / ipc][c]) with gamma / beta (rows, C)
-// f32 and ipc images per context row. The stage kernels take their norm weight as a type NW: `const float*` is the
-// plain stage (signature and code as before), FilmNW adds the modulation. A tile can span images of two context rows
-// (8 x 8 stage: two images per 128 pixels), so gamma / beta are read per pooled pixel, not once per workgroup.
-struct FilmNW {
-  const float* nw;
-  const float* gamma;
-  const float* beta;
-  int ipc;
-};
-template <class NW> constexpr bool is_film = false;
-template <> constexpr bool is_film<FilmNW> = true;
-SD_DEV const float* nw_of(const float* nw) { return nw; }
-SD_DEV const float* nw_of(const FilmNW& f) { return f.nw; }
+// NW, the stage's norm weight (`const float*`, or FilmNW for the FiLM stage): stage_core.h
 template <int BN, int WM, class NW>
 SD_DEV void pool_epilogue(const f32x4 (&acc)[WM / 16][BN / 16], float* C, const GemmArgs& g, const Geom& G, int lw,
                           int lhw, int bm0, NW nw, float* pooled, uint8_t* amax, float* y, float* rstd,
@@ -1126,8 +1111,8 @@ struct WdBf16x3 {
 
 // WS (wave split): for narrow j ranges (the 4-channel first stage: J + 1 = 101 -> 7 blocks) every wave covers all j
 // blocks over every 8th k step, and the 8 waves' tiles are summed through LDS at the end.
-// PL: dy is the max-pool backward's input (pooled resolution + argmax, sd_pool_rms_bwd_compact), expanded while it is
-// fetched — the full-resolution conv gradient (3/4 zeros) is never written to or read from HBM.
+// PL: dy is the max-pool backward's input (pooled resolution + argmax, sd_pool_rms_bwd_compact of poolnorm.hip),
+// expanded while it is fetched — the full-resolution conv gradient (3/4 zeros) is never written to or read from HBM.
 template <class M, int TM, int NBW, bool WS>
 SD_DEV void wgrad_direct_body(const DirectW& d) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1515,9 +1500,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_wide3(GemmArgs g, Geom G, i
 // tiles of 32-pixel waves (MT = 2) with a padded pixel-major patch, two workgroups per CU, was retired: 183 -> 131 us
 // alone on the 64 -> 48 stage (profiles/r06dg3).
 // PL: dout is the max-pool backward's pooled-resolution gradient (Nb, H / 2, W / 2, CIN) and amax the forward's argmax
-// bytes (sd_pool_rms_bwd_compact): the full-resolution dOut (3/4 zeros) exists only in the LDS patch. A thread's item
-// is one pooled element x 4 channels of the pooled rows / columns whose 2x2 windows touch the patch (any parity of the
-// patch's first row and column): one f32x4 + 4 argmax bytes loaded, one split, and each of the window's four positions
+// bytes (sd_pool_rms_bwd_compact, poolnorm.hip): the full-resolution dOut (3/4 zeros) exists only in the LDS patch.
+// A thread's item is one pooled element x 4 channels of the pooled rows / columns whose 2x2 windows touch the patch
+// (any parity of the patch's first row and column): one f32x4 + 4 argmax bytes loaded, one split, and each of the window's four positions
 // inside the patch written with the value where the channel's argmax names the position and zero elsewhere. The
 // windows tile the plane, so every patch slot is written exactly once (pooled indices outside the image write zeros)
 // with the bits the full-resolution form stages there: same products, same k order, the same dIn bit for bit.
@@ -1750,210 +1735,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(GemmArgs g, Geom G, int
   gemm_block<BM, BN, WM, WN>(g, la, lb, bm0, bn0, 0, split, kbeg, kend);
 }
 
-// ---------------------------------------------------------------- pooling / norm epilogues
-// y = silu(rms(maxpool2(x))) per output pixel (team of T lanes, VPT channels each); keeps pooled + argmax.
-template <int T, int VPT, class NW = const float* __restrict__>
-__global__ void pool_rms_fwd(const float* __restrict__ x, NW w, float* __restrict__ pooled,
-                             uint8_t* __restrict__ amax, float* __restrict__ y, float* __restrict__ rstd, int Nb, int H,
-                             int W, int C, float eps, int nchw_flat) {
-  const int Ho = H / 2, Wo = W / 2;
-  const long P = (long)Nb * Ho * Wo;
-  const long pix = ((long)blockIdx.x * blockDim.x + threadIdx.x) / T;
-  const int t = threadIdx.x % T;
-  if (pix >= P) return;
-  const int n = (int)(pix / (Ho * Wo));
-  const int rem = (int)(pix % (Ho * Wo));
-  const int yo = rem / Wo, xo = rem % Wo;
-  float v[VPT];
-  float ss = 0.f;
-#pragma unroll
-  for (int j = 0; j < VPT; ++j) {
-    const int c = t + j * T;
-    v[j] = 0.f;
-    if (c < C) {
-      float best = -INFINITY;
-      int bi = 0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int yy = 2 * yo + (q >> 1), xx = 2 * xo + (q & 1);
-        const float val = x[(((long)n * H + yy) * W + xx) * C + c];
-        if (val > best || isnan(val)) { best = val; bi = q; }
-      }
-      v[j] = best;
-      pooled[pix * C + c] = best;
-      amax[pix * C + c] = (uint8_t)bi;
-    }
-    ss += v[j] * v[j];
-  }
-  ss = group_sum<T>(ss);
-  const float r = rsqrtf(ss / (float)C + eps);
-  if (t == 0) rstd[pix] = r;
-  long fo = 0;
-  if constexpr (is_film<NW>) fo = (long)(n / w.ipc) * C;
-#pragma unroll
-  for (int j = 0; j < VPT; ++j) {
-    const int c = t + j * T;
-    if (c < C) {
-      float z = v[j] * r * nw_of(w)[c];
-      if constexpr (is_film<NW>) z = w.gamma[fo + c] * z + w.beta[fo + c];
-      const long o = nchw_flat ? (long)n * C * Ho * Wo + (long)c * Ho * Wo + rem : pix * C + c;
-      y[o] = siluf_(z);
-    }
-  }
-}
-
-// COMPACT: dx is the pooled-resolution gradient (Nb, H/2, W/2, C) for sd_conv2d_wgrad_pool (no window scatter)
-// FiLM (NW = FilmNW): z = gamma * norm + beta is recomputed, the gradient continues as dnorm = dz * gamma (the norm
-// weight's partials are then sums of dz * gamma * xhat); dgamma / dbeta come from film_grad_partial below.
-template <int T, int VPT, bool COMPACT = false, class NW = const float* __restrict__>
-__global__ void pool_rms_bwd(const float* __restrict__ pooled, const uint8_t* __restrict__ amax,
-                             NW w, const float* __restrict__ rstd, const float* __restrict__ dy,
-                             float* __restrict__ dx, float* __restrict__ dw_part, int Nb, int H, int W, int C,
-                             int nchw_flat) {
-  const int Ho = H / 2, Wo = W / 2;
-  const long P = (long)Nb * Ho * Wo;
-  const int t = threadIdx.x % T;
-  const int team = threadIdx.x / T;
-  constexpr int TPB = 256 / T;
-  float dwacc[VPT];
-#pragma unroll
-  for (int j = 0; j < VPT; ++j) dwacc[j] = 0.f;
-  for (long pix = (long)blockIdx.x * TPB + team; pix < P; pix += (long)gridDim.x * TPB) {
-    const int n = (int)(pix / (Ho * Wo));
-    const int rem = (int)(pix % (Ho * Wo));
-    const int yo = rem / Wo, xo = rem % Wo;
-    const float r = rstd[pix];
-    float xh[VPT], g[VPT];
-    float dot = 0.f;
-    long fo = 0;
-    if constexpr (is_film<NW>) fo = (long)(n / w.ipc) * C;
-#pragma unroll
-    for (int j = 0; j < VPT; ++j) {
-      const int c = t + j * T;
-      xh[j] = g[j] = 0.f;
-      if (c < C) {
-        const float xv = pooled[pix * C + c] * r;
-        const float wv = nw_of(w)[c];
-        float z = xv * wv;
-        if constexpr (is_film<NW>) z = w.gamma[fo + c] * z + w.beta[fo + c];
-        const float s = sigmoidf_(z);
-        const long o = nchw_flat ? (long)n * C * Ho * Wo + (long)c * Ho * Wo + rem : pix * C + c;
-        float dz = dy[o] * s * (1.f + z * (1.f - s));
-        if constexpr (is_film<NW>) dz *= w.gamma[fo + c];
-        xh[j] = xv;
-        g[j] = dz * wv;
-        dwacc[j] += dz * xv;
-        dot += g[j] * xv;
-      }
-    }
-    dot = group_sum<T>(dot) / (float)C;
-#pragma unroll
-    for (int j = 0; j < VPT; ++j) {
-      const int c = t + j * T;
-      if (c < C) {
-        const float dp = r * (g[j] - xh[j] * dot);
-        if constexpr (COMPACT) {
-          dx[pix * C + c] = dp;
-        } else {
-          const int bi = amax[pix * C + c];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int yy = 2 * yo + (q >> 1), xx = 2 * xo + (q & 1);
-            dx[(((long)n * H + yy) * W + xx) * C + c] = q == bi ? dp : 0.f;
-          }
-          // an odd H or W: MaxPool2d(2) floors, so the last row / column belongs to no window and its gradient is
-          // zero. The windows at the edge write it (dx is not cleared beforehand); even sizes take neither branch.
-          const bool ex = (W & 1) && xo == Wo - 1, ey = (H & 1) && yo == Ho - 1;
-          if (ex) {
-            dx[(((long)n * H + 2 * yo) * W + W - 1) * C + c] = 0.f;
-            dx[(((long)n * H + 2 * yo + 1) * W + W - 1) * C + c] = 0.f;
-          }
-          if (ey) {
-            dx[(((long)n * H + H - 1) * W + 2 * xo) * C + c] = 0.f;
-            dx[(((long)n * H + H - 1) * W + 2 * xo + 1) * C + c] = 0.f;
-            if (ex) dx[(((long)n * H + H - 1) * W + W - 1) * C + c] = 0.f;
-          }
-        }
-      }
-    }
-  }
-  // per-block dw partials
-  __shared__ float wp[TPB * T * VPT];
-#pragma unroll
-  for (int j = 0; j < VPT; ++j) wp[(team * VPT + j) * T + t] = dwacc[j];
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const int j = c / T, tt = c % T;
-    float s = 0.f;
-    for (int tm = 0; tm < TPB; ++tm) s += wp[(tm * VPT + j) * T + tt];
-    dw_part[(long)blockIdx.x * C + c] = s;
-  }
-}
-
-// FiLM parameter gradients of a stage, first pass: workgroup (blk, b) walks context row b's ipc * Ho * Wo pooled pixels
-// (16 teams of 16 lanes, VPT channels per lane, as pool_rms_bwd), recomputes dz = dy * silu'(gamma * norm + beta) and
-// keeps S0 = sum dz, S1 = sum dz * xhat per channel; the 16 teams are added in team order and the block's sums go to
-// part[b][blk][2][C]. film_grad_final adds the blocks in block order: dbeta = S0, dgamma = nw * S1 (norm = xhat * nw).
-// No atomics: the result does not depend on the schedule.
-template <int T, int VPT>
-__global__ __launch_bounds__(256) void film_grad_partial(const float* __restrict__ pooled, const FilmNW w,
-                                                         const float* __restrict__ rstd,
-                                                         const float* __restrict__ dy, float* __restrict__ part,
-                                                         int Ho, int Wo, int C, int nchw_flat) {
-  const int t = threadIdx.x % T, team = threadIdx.x / T, b = blockIdx.y;
-  constexpr int TPB = 256 / T;
-  const int hw = Ho * Wo;
-  const long rowpix = (long)w.ipc * hw, pix0 = (long)b * rowpix;
-  float s0[VPT], s1[VPT];
-#pragma unroll
-  for (int j = 0; j < VPT; ++j) s0[j] = s1[j] = 0.f;
-  for (long lp = (long)blockIdx.x * TPB + team; lp < rowpix; lp += (long)gridDim.x * TPB) {
-    const long pix = pix0 + lp;
-    const int n = (int)(pix / hw), rem = (int)(pix % hw);
-    const float r = rstd[pix];
-#pragma unroll
-    for (int j = 0; j < VPT; ++j) {
-      const int c = t + j * T;
-      if (c < C) {
-        const float xv = pooled[pix * C + c] * r;
-        const float z = w.gamma[(long)b * C + c] * (xv * w.nw[c]) + w.beta[(long)b * C + c];
-        const float s = sigmoidf_(z);
-        const long o = nchw_flat ? (long)n * C * hw + (long)c * hw + rem : pix * C + c;
-        const float dz = dy[o] * s * (1.f + z * (1.f - s));
-        s0[j] += dz;
-        s1[j] += dz * xv;
-      }
-    }
-  }
-  __shared__ float sp[2][TPB * T * VPT];
-#pragma unroll
-  for (int j = 0; j < VPT; ++j) {
-    sp[0][(team * VPT + j) * T + t] = s0[j];
-    sp[1][(team * VPT + j) * T + t] = s1[j];
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * C; i += 256) {
-    const int k = i / C, c = i % C, j = c / T, tt = c % T;
-    float s = 0.f;
-    for (int tm = 0; tm < TPB; ++tm) s += sp[k][(tm * VPT + j) * T + tt];
-    part[(((long)b * gridDim.x + blockIdx.x) * 2 + k) * C + c] = s;
-  }
-}
-
-__global__ void film_grad_final(const float* __restrict__ part, const float* __restrict__ nw,
-                                float* __restrict__ dgamma, float* __restrict__ dbeta, int rows, int nblk, int C) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows * C) return;
-  const int b = i / C, c = i % C;
-  float s0 = 0.f, s1 = 0.f;
-  for (int k = 0; k < nblk; ++k) {
-    s0 += part[(((long)b * nblk + k) * 2 + 0) * C + c];
-    s1 += part[(((long)b * nblk + k) * 2 + 1) * C + c];
-  }
-  dbeta[i] = s0;
-  dgamma[i] = s1 * nw[c];
-}
-
+// ---------------------------------------------------------------- weight flip, upsample backward
 // Wf[ci][ky][kx][co] = W[co][kh-1-ky][kw-1-kx][ci]
 __global__ void flip_weight(const float* __restrict__ w, float* __restrict__ wf, int Co, int kh, int kw, int Ci) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1998,8 +1780,6 @@ void wgrad_tile(GemmArgs& g, Geom& G, int J, bool va, bool vb, hipStream_t s) {
   with_bools([&](auto VA, auto VB) { conv_wgrad_kernel<BM, BN, WM, WN, VA(), VB()><<<grid, 256, 0, s>>>(g, G, J); },
              va, vb);
 }
-
-int vpt_for(int C, int T) { int v = (C + T - 1) / T; return v <= 1 ? 1 : v <= 2 ? 2 : v <= 4 ? 4 : 8; }
 
 // ---------------------------------------------------------------- direct bwd-weight: host plans and launcher
 // row-block size, j blocking, split count (shared with the workspace queries) and the staging geometry
@@ -2122,10 +1902,6 @@ template <bool X3, int TM, int NBW, bool WS, bool PL>
 constexpr auto wd_kernel() {
   if constexpr (X3) return &conv_wgrad3_direct<TM, NBW, WS, PL>;
   else return &conv_wgrad_direct<TM, NBW, WS, PL>;
-}
-template <int... Vs, class F>
-void with_int(int v, F&& f) {  // f(std::integral_constant<int, V>) for the V of the list that equals v
-  ((v == Vs ? f(std::integral_constant<int, Vs>{}) : void()), ...);
 }
 
 // One launch of the plan's rung on the f32 or the split-bf16 (X3) kernel, then the fixed-order sum of its slabs.
@@ -2315,7 +2091,8 @@ extern "C" int sd_conv2d_wgrad_slabs(int Nb, int Hs, int Ws, int Ci, int Co, int
 }
 
 // bwd-weight of a pooled stage straight from the max-pool backward's pooled-resolution gradient + argmax
-// (sd_pool_rms_bwd_compact): the direct f32 kernel expands it while staging. SD_ESHAPE outside the direct plan.
+// (sd_pool_rms_bwd_compact, poolnorm.hip): the direct f32 kernel expands it while staging. SD_ESHAPE outside the
+// direct plan.
 extern "C" int sd_conv2d_wgrad_pool_slabs(int Nb, int H, int W, int Ci, int Co, int kh, int kw) {
   DirectPlan pl;
   if (!pool_plan(Nb, H, W, Ci, Co, kh, kw, pl)) return 0;
@@ -2350,150 +2127,6 @@ extern "C" int sd_sumpool2(const float* du, float* din, int Nb, int H, int W, in
   sumpool2<<<(int)((total + 255) / 256), 256, 0, (hipStream_t)s>>>(du, din, Nb, H, W, C);
   SD_LAUNCH_CHECK();
   return SD_OK;
-}
-
-#define SD_POOL_SWITCH(KERNEL, GRID, ...)                                                  \
-  switch (vpt_for(C, 16)) {                                                                 \
-    case 1: KERNEL<16, 1><<<GRID, 256, 0, s>>>(__VA_ARGS__); break;                          \
-    case 2: KERNEL<16, 2><<<GRID, 256, 0, s>>>(__VA_ARGS__); break;                          \
-    case 4: KERNEL<16, 4><<<GRID, 256, 0, s>>>(__VA_ARGS__); break;                          \
-    default: KERNEL<16, 8><<<GRID, 256, 0, s>>>(__VA_ARGS__); break;                         \
-  }
-
-extern "C" int sd_pool_rms_fwd(const float* x, const float* w, float* pooled, uint8_t* amax, float* y, float* rstd,
-                               int Nb, int H, int W, int C, float eps, int nchw_flat, sd_stream stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  if (C > 128) return SD_ESHAPE;
-  const long P = (long)Nb * (H / 2) * (W / 2);
-  if (P <= 0) return SD_OK;
-  const int grid = (int)((P * 16 + 255) / 256);
-  SD_POOL_SWITCH(pool_rms_fwd, grid, x, w, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat)
-  SD_LAUNCH_CHECK();
-  return SD_OK;
-}
-
-// An image of one row or one column has no 2x2 window: the conv gradient is all zeros and no pooled pixel exists to
-// write it (the degenerate case only; every other shape is written by the kernel itself, odd edges included).
-static int pool_rms_bwd_empty(float* dx, int Nb, int H, int W, int C, hipStream_t s) {
-  const long n = (long)Nb * H * W * C;
-  if (n <= 0 || ((H / 2) > 0 && (W / 2) > 0)) return SD_OK;
-  return hipMemsetAsync(dx, 0, (size_t)n * sizeof(float), s) == hipSuccess ? SD_OK : SD_EARG;
-}
-
-extern "C" int sd_pool_rms_bwd_blocks(int Nb, int H, int W) {
-  const long P = (long)Nb * (H / 2) * (W / 2);
-  long b = (P + 15) / 16;
-  return (int)(b < 2048 ? (b > 0 ? b : 1) : 2048);
-}
-
-extern "C" int sd_pool_rms_bwd(const float* pooled, const uint8_t* amax, const float* w, const float* rstd,
-                               const float* dy, float* dx, float* dw, float* dw_partial, int Nb, int H, int W, int C,
-                               int nchw_flat, int accumulate_dw, sd_stream stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  if (C > 128) return SD_ESHAPE;
-  const int grid = sd_pool_rms_bwd_blocks(Nb, H, W);
-  if (pool_rms_bwd_empty(dx, Nb, H, W, C, s) != SD_OK) return SD_EARG;
-  SD_POOL_SWITCH(pool_rms_bwd, grid, pooled, amax, w, rstd, dy, dx, dw_partial, Nb, H, W, C, nchw_flat)
-  SD_LAUNCH_CHECK();
-  // two-pass column sum of the per-block dw partials; its chunk workspace follows them in dw_partial
-  return sd_colsum_ws(dw_partial, dw, grid, C, C, accumulate_dw, dw_partial + (long)grid * C, stream_);
-}
-
-extern "C" int sd_pool_rms_bwd_compact(const float* pooled, const uint8_t* amax, const float* w, const float* rstd,
-                                       const float* dy, float* dpool, float* dw, float* dw_partial, int Nb, int H,
-                                       int W, int C, int nchw_flat, int accumulate_dw, sd_stream stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  if (C > 128) return SD_ESHAPE;
-  const int grid = sd_pool_rms_bwd_blocks(Nb, H, W);
-  switch (vpt_for(C, 16)) {
-    case 1: pool_rms_bwd<16, 1, true><<<grid, 256, 0, s>>>(pooled, amax, w, rstd, dy, dpool, dw_partial, Nb, H, W, C, nchw_flat); break;
-    case 2: pool_rms_bwd<16, 2, true><<<grid, 256, 0, s>>>(pooled, amax, w, rstd, dy, dpool, dw_partial, Nb, H, W, C, nchw_flat); break;
-    case 4: pool_rms_bwd<16, 4, true><<<grid, 256, 0, s>>>(pooled, amax, w, rstd, dy, dpool, dw_partial, Nb, H, W, C, nchw_flat); break;
-    default: pool_rms_bwd<16, 8, true><<<grid, 256, 0, s>>>(pooled, amax, w, rstd, dy, dpool, dw_partial, Nb, H, W, C, nchw_flat); break;
-  }
-  SD_LAUNCH_CHECK();
-  return sd_colsum_ws(dw_partial, dw, grid, C, C, accumulate_dw, dw_partial + (long)grid * C, stream_);
-}
-
-// FiLM stage: the two-launch forward, and the backward (dnorm through gamma, then sd_pool_rms_bwd's own chain; dgamma /
-// dbeta (rows, C) by film_grad_partial + film_grad_final, overwritten). film_partial >= sd_film_grad_floats floats.
-extern "C" int sd_pool_rms_fwd_film(const float* x, const float* w, const float* gamma, const float* beta, int ipc,
-                                    float* pooled, uint8_t* amax, float* y, float* rstd, int Nb, int H, int W, int C,
-                                    float eps, int nchw_flat, sd_stream stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  if (C > 128) return SD_ESHAPE;
-  if (!gamma || !beta || ipc <= 0 || Nb % ipc) return SD_EARG;
-  const long P = (long)Nb * (H / 2) * (W / 2);
-  if (P <= 0) return SD_OK;
-  const int grid = (int)((P * 16 + 255) / 256);
-  const FilmNW f{w, gamma, beta, ipc};
-  switch (vpt_for(C, 16)) {
-    case 1: pool_rms_fwd<16, 1, FilmNW><<<grid, 256, 0, s>>>(x, f, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat); break;
-    case 2: pool_rms_fwd<16, 2, FilmNW><<<grid, 256, 0, s>>>(x, f, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat); break;
-    case 4: pool_rms_fwd<16, 4, FilmNW><<<grid, 256, 0, s>>>(x, f, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat); break;
-    default: pool_rms_fwd<16, 8, FilmNW><<<grid, 256, 0, s>>>(x, f, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat); break;
-  }
-  SD_LAUNCH_CHECK();
-  return SD_OK;
-}
-
-static int film_grad_blocks(int ipc, int H, int W) {
-  const long b = ((long)ipc * (H / 2) * (W / 2) + 15) / 16;
-  return (int)(b < 64 ? (b > 0 ? b : 1) : 64);
-}
-
-extern "C" int sd_film_grad_floats(int Nb, int ipc, int H, int W, int C) {
-  if (ipc <= 0) return 0;
-  return (Nb / ipc) * film_grad_blocks(ipc, H, W) * 2 * C;
-}
-
-template <bool COMPACT>
-static int pool_rms_bwd_film_impl(const float* pooled, const uint8_t* amax, const float* w, const float* gamma,
-                                  const float* beta, int ipc, const float* rstd, const float* dy, float* dx, float* dw,
-                                  float* dw_partial, float* dgamma, float* dbeta, float* film_partial, int Nb, int H,
-                                  int W, int C, int nchw_flat, int accumulate_dw, sd_stream stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  if (C > 128) return SD_ESHAPE;
-  if (!gamma || !beta || !dgamma || !dbeta || !film_partial || ipc <= 0 || Nb % ipc) return SD_EARG;
-  if (Nb <= 0) return SD_OK;
-  const int grid = sd_pool_rms_bwd_blocks(Nb, H, W);
-  const FilmNW f{w, gamma, beta, ipc};
-  const int rows = Nb / ipc, nblk = film_grad_blocks(ipc, H, W);
-  if (!COMPACT && pool_rms_bwd_empty(dx, Nb, H, W, C, s) != SD_OK) return SD_EARG;
-  const dim3 fgrid(nblk, rows);
-#define SD_FILM_BWD(V)                                                                                               \
-  pool_rms_bwd<16, V, COMPACT, FilmNW><<<grid, 256, 0, s>>>(pooled, amax, f, rstd, dy, dx, dw_partial, Nb, H, W, C,  \
-                                                            nchw_flat);                                              \
-  SD_LAUNCH_CHECK();                                                                                                 \
-  film_grad_partial<16, V><<<fgrid, 256, 0, s>>>(pooled, f, rstd, dy, film_partial, H / 2, W / 2, C, nchw_flat)
-  switch (vpt_for(C, 16)) {
-    case 1: SD_FILM_BWD(1); break;
-    case 2: SD_FILM_BWD(2); break;
-    case 4: SD_FILM_BWD(4); break;
-    default: SD_FILM_BWD(8); break;
-  }
-#undef SD_FILM_BWD
-  SD_LAUNCH_CHECK();
-  film_grad_final<<<sd_cdiv((long)rows * C, 256), 256, 0, s>>>(film_partial, w, dgamma, dbeta, rows, nblk, C);
-  SD_LAUNCH_CHECK();
-  return sd_colsum_ws(dw_partial, dw, grid, C, C, accumulate_dw, dw_partial + (long)grid * C, stream_);
-}
-
-extern "C" int sd_pool_rms_bwd_film(const float* pooled, const uint8_t* amax, const float* w, const float* gamma,
-                                    const float* beta, int ipc, const float* rstd, const float* dy, float* dx,
-                                    float* dw, float* dw_partial, float* dgamma, float* dbeta, float* film_partial,
-                                    int Nb, int H, int W, int C, int nchw_flat, int accumulate_dw, sd_stream stream_) {
-  return pool_rms_bwd_film_impl<false>(pooled, amax, w, gamma, beta, ipc, rstd, dy, dx, dw, dw_partial, dgamma, dbeta,
-                                       film_partial, Nb, H, W, C, nchw_flat, accumulate_dw, stream_);
-}
-
-extern "C" int sd_pool_rms_bwd_compact_film(const float* pooled, const uint8_t* amax, const float* w,
-                                            const float* gamma, const float* beta, int ipc, const float* rstd,
-                                            const float* dy, float* dpool, float* dw, float* dw_partial, float* dgamma,
-                                            float* dbeta, float* film_partial, int Nb, int H, int W, int C,
-                                            int nchw_flat, int accumulate_dw, sd_stream stream_) {
-  return pool_rms_bwd_film_impl<true>(pooled, amax, w, gamma, beta, ipc, rstd, dy, dpool, dw, dw_partial, dgamma,
-                                      dbeta, film_partial, Nb, H, W, C, nchw_flat, accumulate_dw, stream_);
 }
 
 extern "C" int sd_conv2d_dgrad_bf16x3(const float* dout, const float* wflip, float* din, int Nb, int Hs, int Ws,
@@ -2854,106 +2487,6 @@ extern "C" int sd_conv2d_dgrad_pool(const float* dpool, const uint8_t* amax, con
   SD_LAUNCH_CHECK();
   return SD_OK;
 }
-
-// ---------------------------------------------------------------- wide stages: row kernels, 128 < C <= 512
-// pool_rms_fwd / pool_rms_bwd / film_grad_partial with a whole wave per pooled pixel (T = 64, 4 or 8 channels per
-// lane): the same code line for line, ss and dot summed over the 64 lanes, 4 pixels per workgroup step. The narrow
-// entries keep refusing C > 128; these refuse everything else, before any launch.
-static bool wide_rows(int C) { return C > 128 && C <= SD_POOL_WIDE_MAX; }
-
-#define SD_WIDE_SWITCH(LAUNCH)                \
-  if (vpt_for(C, 64) <= 4) { LAUNCH(4); }     \
-  else { LAUNCH(8); }
-
-template <class NW>
-static int pool_rms_wide_fwd_impl(const float* x, NW w, float* pooled, uint8_t* amax, float* y, float* rstd, int Nb,
-                                  int H, int W, int C, float eps, int nchw_flat, hipStream_t s) {
-  const long P = (long)Nb * (H / 2) * (W / 2);
-  if (P <= 0) return SD_OK;
-  if ((P + 3) / 4 > 0x7fffffffL) return SD_ESHAPE;
-  const int grid = (int)((P + 3) / 4);
-#define SD_L(V) pool_rms_fwd<64, V, NW><<<grid, 256, 0, s>>>(x, w, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat)
-  SD_WIDE_SWITCH(SD_L)
-#undef SD_L
-  SD_LAUNCH_CHECK();
-  return SD_OK;
-}
-
-extern "C" int sd_pool_rms_wide_fwd(const float* x, const float* w, float* pooled, uint8_t* amax, float* y,
-                                    float* rstd, int Nb, int H, int W, int C, float eps, int nchw_flat,
-                                    sd_stream stream_) {
-  if (!wide_rows(C)) return SD_ESHAPE;
-  return pool_rms_wide_fwd_impl<const float*>(x, w, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat,
-                                              (hipStream_t)stream_);
-}
-
-extern "C" int sd_pool_rms_wide_fwd_film(const float* x, const float* w, const float* gamma, const float* beta,
-                                         int ipc, float* pooled, uint8_t* amax, float* y, float* rstd, int Nb, int H,
-                                         int W, int C, float eps, int nchw_flat, sd_stream stream_) {
-  if (!wide_rows(C)) return SD_ESHAPE;
-  if (!gamma || !beta || ipc <= 0 || Nb % ipc) return SD_EARG;
-  return pool_rms_wide_fwd_impl(x, FilmNW{w, gamma, beta, ipc}, pooled, amax, y, rstd, Nb, H, W, C, eps, nchw_flat,
-                                (hipStream_t)stream_);
-}
-
-extern "C" int sd_pool_rms_wide_bwd_blocks(int Nb, int H, int W) {
-  const long P = (long)Nb * (H / 2) * (W / 2);
-  const long b = (P + 3) / 4;
-  return (int)(b < 2048 ? (b > 0 ? b : 1) : 2048);
-}
-
-static int film_grad_wide_blocks(int ipc, int H, int W) {
-  const long b = ((long)ipc * (H / 2) * (W / 2) + 3) / 4;
-  return (int)(b < 64 ? (b > 0 ? b : 1) : 64);
-}
-
-extern "C" int sd_film_grad_wide_floats(int Nb, int ipc, int H, int W, int C) {
-  if (ipc <= 0) return 0;
-  return (Nb / ipc) * film_grad_wide_blocks(ipc, H, W) * 2 * C;
-}
-
-extern "C" int sd_pool_rms_wide_bwd(const float* pooled, const uint8_t* amax, const float* w, const float* rstd,
-                                    const float* dy, float* dx, float* dw, float* dw_partial, int Nb, int H, int W,
-                                    int C, int nchw_flat, int accumulate_dw, sd_stream stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  if (!wide_rows(C)) return SD_ESHAPE;
-  const int grid = sd_pool_rms_wide_bwd_blocks(Nb, H, W);
-  if (pool_rms_bwd_empty(dx, Nb, H, W, C, s) != SD_OK) return SD_EARG;
-#define SD_L(V) \
-  pool_rms_bwd<64, V><<<grid, 256, 0, s>>>(pooled, amax, w, rstd, dy, dx, dw_partial, Nb, H, W, C, nchw_flat)
-  SD_WIDE_SWITCH(SD_L)
-#undef SD_L
-  SD_LAUNCH_CHECK();
-  return sd_colsum_ws(dw_partial, dw, grid, C, C, accumulate_dw, dw_partial + (long)grid * C, stream_);
-}
-
-extern "C" int sd_pool_rms_wide_bwd_film(const float* pooled, const uint8_t* amax, const float* w, const float* gamma,
-                                         const float* beta, int ipc, const float* rstd, const float* dy, float* dx,
-                                         float* dw, float* dw_partial, float* dgamma, float* dbeta,
-                                         float* film_partial, int Nb, int H, int W, int C, int nchw_flat,
-                                         int accumulate_dw, sd_stream stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  if (!wide_rows(C)) return SD_ESHAPE;
-  if (!gamma || !beta || !dgamma || !dbeta || !film_partial || ipc <= 0 || Nb % ipc) return SD_EARG;
-  if (Nb <= 0) return SD_OK;
-  const int grid = sd_pool_rms_wide_bwd_blocks(Nb, H, W);
-  const FilmNW f{w, gamma, beta, ipc};
-  const int rows = Nb / ipc, nblk = film_grad_wide_blocks(ipc, H, W);
-  if (pool_rms_bwd_empty(dx, Nb, H, W, C, s) != SD_OK) return SD_EARG;
-  const dim3 fgrid(nblk, rows);
-#define SD_L(V)                                                                                                     \
-  pool_rms_bwd<64, V, false, FilmNW><<<grid, 256, 0, s>>>(pooled, amax, f, rstd, dy, dx, dw_partial, Nb, H, W, C,   \
-                                                          nchw_flat);                                               \
-  SD_LAUNCH_CHECK();                                                                                                \
-  film_grad_partial<64, V><<<fgrid, 256, 0, s>>>(pooled, f, rstd, dy, film_partial, H / 2, W / 2, C, nchw_flat)
-  SD_WIDE_SWITCH(SD_L)
-#undef SD_L
-  SD_LAUNCH_CHECK();
-  film_grad_final<<<sd_cdiv((long)rows * C, 256), 256, 0, s>>>(film_partial, w, dgamma, dbeta, rows, nblk, C);
-  SD_LAUNCH_CHECK();
-  return sd_colsum_ws(dw_partial, dw, grid, C, C, accumulate_dw, dw_partial + (long)grid * C, stream_);
-}
-#undef SD_WIDE_SWITCH
 
 // ---------------------------------------------------------------- wide stages: split-bf16 backward contractions
 // Shapes with a channel count above 128 (every older split-bf16 arm refuses them), pixel and tile counts in int range.

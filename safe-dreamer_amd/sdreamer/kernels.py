@@ -1035,18 +1035,22 @@ def _stage_outputs(Nb, H, W, C, device):
     return torch.empty_like(pooled), pooled, amax, torch.empty(Nb, H // 2, W // 2, dtype=torch.float32, device=device)
 
 
-def pool_rms_fwd(x, w, nchw_flat=False, film=None):
-    """film = (gamma, beta): the FiLM stage, z = gamma[n // ipc] * norm + beta[n // ipc] before the SiLU"""
+def _pool_rms_fwd(stem, x, w, nchw_flat, film):
+    """pool_rms_fwd / pool_rms_wide_fwd: entry `stem` (`stem`_film with film) -> (y, pooled, amax, rstd)"""
     Nb, H, W, C = x.shape
     y, pooled, amax, rstd = _stage_outputs(Nb, H, W, C, x.device)
+    sfx, fa = "", ()
     if film is not None:
         gamma, beta, ipc = _film_args(film, Nb, C)
-        nat.call("sd_pool_rms_fwd_film", p(_c(x)), p(w), p(gamma), p(beta), ipc, p(pooled), p(amax), p(y), p(rstd),
-                 Nb, H, W, C, EPS, int(nchw_flat), stream())
-        return y, pooled, amax, rstd
-    nat.call("sd_pool_rms_fwd", p(_c(x)), p(w), p(pooled), p(amax), p(y), p(rstd), Nb, H, W, C, EPS, int(nchw_flat),
+        sfx, fa = "_film", (p(gamma), p(beta), ipc)
+    nat.call(stem + sfx, p(_c(x)), p(w), *fa, p(pooled), p(amax), p(y), p(rstd), Nb, H, W, C, EPS, int(nchw_flat),
              stream())
     return y, pooled, amax, rstd
+
+
+def pool_rms_fwd(x, w, nchw_flat=False, film=None):
+    """film = (gamma, beta): the FiLM stage, z = gamma[n // ipc] * norm + beta[n // ipc] before the SiLU"""
+    return _pool_rms_fwd("sd_pool_rms_fwd", x, w, nchw_flat, film)
 
 
 def ops_fused_pool():
@@ -1118,15 +1122,7 @@ WIDE_ROWS_MAX = nat._define(nat.HEADER, "SD_POOL_WIDE_MAX")
 
 def pool_rms_wide_fwd(x, w, nchw_flat=False, film=None):
     """pool_rms_fwd for WIDE_ROWS_MIN < C <= WIDE_ROWS_MAX (sd_pool_rms_wide_fwd[_film]): same outputs, same meaning"""
-    Nb, H, W, C = x.shape
-    y, pooled, amax, rstd = _stage_outputs(Nb, H, W, C, x.device)
-    sfx, fa = "", ()
-    if film is not None:
-        gamma, beta, ipc = _film_args(film, Nb, C)
-        sfx, fa = "_film", (p(gamma), p(beta), ipc)
-    nat.call("sd_pool_rms_wide_fwd" + sfx, p(_c(x)), p(w), *fa, p(pooled), p(amax), p(y), p(rstd), Nb, H, W, C, EPS,
-             int(nchw_flat), stream())
-    return y, pooled, amax, rstd
+    return _pool_rms_fwd("sd_pool_rms_wide_fwd", x, w, nchw_flat, film)
 
 
 def pool_rms_wide_bwd(pooled, amax, w, rstd, dy, H, W, dw, nchw_flat=False, film=None):

@@ -1,5 +1,5 @@
 """Small conv encoder / decoder stage cases for pinning csrc/conv.hip (every forward, weight-gradient and
-input-gradient kernel and the host plans that pick among them) to a float64 reference at every kind of shape the
+input-gradient kernel and the host plans that pick among them) and the stage's row kernels in csrc/poolnorm.hip to a float64 reference at every kind of shape the
 Python surface admits, not only the BASELINE stages. Test infrastructure (a plain module: no fixtures, no hooks).
 
 Shared by tests/test_conv_parity_cpu.py (the tie margin, the float32 restatement against float64, mutated references,

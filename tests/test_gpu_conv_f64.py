@@ -1,6 +1,6 @@
 """The conv encoder / decoder stages (ops.ConvPoolNormFn, ops.FilmConvPoolNormFn, ops.UpConvFn + ops.rms_silu) and the
 conv entry points of kernels.py against a float64 torch reference, at the smallest shapes that reach each arm of
-csrc/conv.hip's dispatch (tests/conv_models.py: the case tables, with the arm each case reaches; the tie margin, the
+csrc/conv.hip's dispatch and of the row kernels' in csrc/poolnorm.hip (tests/conv_models.py: the case tables, with the arm each case reaches; the tie margin, the
 comparison functions and their discrimination are checked on the CPU by test_conv_parity_cpu.py; DESIGN.md § 2.2 has
 the table and the measured figures).
 

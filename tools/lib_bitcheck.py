@@ -1,6 +1,7 @@
 """Bit-identity check between two builds of libsdhip.so (A/B aid): computes the split-bf16 and f32 conv bwd-weight, the
 pooled-gradient bwd-weight on both, the split-bf16 bwd-data, every output of the distribution-head kernels (csrc/dist.hip)
-over the case tables of tests/rowop_models.py, the fused imagination of the bench agent (random init, seed 0) and the
+over the case tables of tests/rowop_models.py, every output of the pool / RMSNorm row entries (csrc/poolnorm.hip) at
+each of their dispatch arms, the fused imagination of the bench agent (random init, seed 0) and the
 parameters after two eager updates of that agent on the bench's synthetic buffer, on fixed inputs, with the library
 SDHIP_LIB points at, and saves them to argv[1]; `python tools/lib_bitcheck.py cmp a.npz b.npz` reports whether every array is bit-identical."""
 import os
@@ -37,11 +38,48 @@ def rowops(res):
         res[f"bnormal_sample/{rows}x{A}/dx"] = K.bnormal_sample_bwd(d_an.cuda(), xd, act, *args).cpu().numpy()
 
 
+def rows(res):
+    """every output of the pool / RMSNorm row entries (csrc/poolnorm.hip) through their kernels.py wrappers, at the
+    smallest shape that reaches each arm: narrow C 9 / 32 / 48 / 128 (1 / 2 / 4 / 8 channels per lane), wide C 154 / 308
+    (4 / 8), plain and FiLM (ipc 2), both output layouts, forward, backward and (narrow) the compact backward"""
+    import torch
+    from sdreamer import kernels as K
+    for C in (9, 32, 48, 128, 154, 308):
+        wide = C > K.WIDE_ROWS_MIN
+        fwd, bwd = (K.pool_rms_wide_fwd, K.pool_rms_wide_bwd) if wide else (K.pool_rms_fwd, K.pool_rms_bwd)
+        for Nb, H, W in ((4, 6, 6), (4, 5, 7)):
+            g = torch.Generator().manual_seed(1000 * C + 10 * H + W)
+            x = torch.randn(Nb, H, W, C, generator=g).cuda()
+            w = (1 + 0.1 * torch.randn(C, generator=g)).cuda()
+            film = ((1 + 0.2 * torch.randn(Nb // 2, C, generator=g)).cuda(),
+                    (0.2 * torch.randn(Nb // 2, C, generator=g)).cuda())
+            dy = torch.randn(Nb, H // 2, W // 2, C, generator=g)
+            for fl in (None, film):
+                for flat in (False, True):
+                    key = f"rows/C{C}_{H}x{W}_{'film' if fl else 'plain'}_{'nchw' if flat else 'nhwc'}"
+                    y, pooled, amax, rstd = fwd(x, w, nchw_flat=flat, film=fl)
+                    d = (dy.permute(0, 3, 1, 2).reshape(Nb, -1) if flat else dy).contiguous().cuda()
+                    outs = {"y": y, "pooled": pooled, "amax": amax, "rstd": rstd}
+                    forms = [("bwd", lambda dw: bwd(pooled, amax, w, rstd, d, H, W, dw, nchw_flat=flat, film=fl))]
+                    if not wide:
+                        forms.append(("compact", lambda dw: K.pool_rms_bwd_compact(pooled, amax, w, rstd, d, dw,
+                                                                                   nchw_flat=flat, film=fl)))
+                    for name, call in forms:
+                        dw = torch.zeros(C, device="cuda")
+                        r = call(dw)
+                        outs[f"{name}_dw"] = dw
+                        for k, v in zip(("grad", "dgamma", "dbeta"), r if fl else (r,)):
+                            outs[f"{name}_{k}"] = v
+                    for k, v in outs.items():
+                        res[f"{key}/{k}"] = v.cpu().numpy()
+
+
 def run(out):
     import torch
     from sdreamer import kernels as K
     res = {}
     rowops(res)
+    rows(res)
     for ci, co, hw, nb in [(32, 48, 32, 64), (48, 64, 16, 64), (64, 64, 8, 64), (4, 32, 64, 8)]:
         g = torch.Generator().manual_seed(ci * 7 + co)
         x = (torch.rand(nb, hw, hw, ci, generator=g) - 0.5).cuda()
@@ -86,8 +124,9 @@ def cmp(a, b):
     za, zb = np.load(a), np.load(b)
     ok = True
     for k in za.files:
-        same = np.array_equal(za[k].view(np.uint32), zb[k].view(np.uint32))
-        print(f"{k}: {'bit-identical' if same else 'DIFFERENT max abs %.3g' % np.abs(za[k] - zb[k]).max()}")
+        same = za[k].shape == zb[k].shape and za[k].dtype == zb[k].dtype and za[k].tobytes() == zb[k].tobytes()
+        diff = np.abs(za[k].astype(np.float64) - zb[k]).max() if za[k].shape == zb[k].shape else float("nan")
+        print(f"{k}: {'bit-identical' if same else 'DIFFERENT max abs %.3g' % diff}")
         ok &= same
     print("ALL BIT-IDENTICAL" if ok else "MISMATCH")
     return 0 if ok else 1
