@@ -35,7 +35,7 @@ int sd_abi_version(void);
  * Replaces nn.Linear fwd/bwd (networks.py:325,348-362; rssm.py:16-32,106-130), BlockLinear.forward's
  * einsum (networks.py:52) as a batch over blocks, Projector (networks.py:380-387) and torch.mm in the
  * Barlow loss (dreamer.py:528). ksplit > 1 needs workspace >= ksplit*batch*M*N floats (deterministic reduce).
- * tile: -1 auto, 0: 128x128, 1: 64x64, 2: 32x128, 3: 128x64. */
+ * tile: -1 auto, 0: 128x128, 1: 64x64, 2: 32x128, 3: 128x64; above 3: SD_EARG (every entry of this section). */
 typedef struct sd_gemm_desc {
   const float* A;
   const float* B;
@@ -70,7 +70,8 @@ int sd_gemm_bf16x3_wgrad2(const sd_gemm_desc* d, float* workspace, long workspac
  * K a multiple of 32, beta 0, no split-K. norm_w null: A used as is. Otherwise rstd(row m) = 1 / sqrt(sum_q
  * part_in[b][q][m] / K + eps) from the producer's npart_in partial sums of squares per row, act 1 = SiLU (0: none).
  * part_out (N % 64 == 0) receives this layer's partials, (N / 64, M) per batch entry: part_out[b][n / 64][m] =
- * sum of C[b][m][n'] ^ 2 over the 64 columns n' of block n / 64. Returns SD_ESHAPE outside these shapes.
+ * sum of C[b][m][n'] ^ 2 over the 64 columns n' of block n / 64 (stride_part_out >= (N / 64) * M at batch > 1, else
+ * SD_EARG). Returns SD_ESHAPE outside these shapes.
  * Per-entry operands (batch <= SD_MLP_MAXB): a non-null w_ptr[b] / bias_ptr[b] / norm_w_ptr[b] replaces
  * B + b * strideB / bias + b * strideBias / norm_w + b * stride_norm_w (each weight (w_rows[b], K) row-major with row
  * stride ldb), and w_rows[b] > 0 limits entry b's weight to that many rows: its columns n >= w_rows[b] of C get 0

@@ -183,7 +183,7 @@ void launch_skinny(const GemmArgs& g, bool bk, bool va, bool vb, hipStream_t st)
 
 extern "C" int sd_gemm_f32(const sd_gemm_desc* d, float* workspace, long workspace_floats, sd_stream stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!d || !d->A || !d->B || !d->C) return SD_EARG;
+  if (!d || !d->A || !d->B || !d->C || d->tile > 3) return SD_EARG;  // (tile: -1 auto, 0 .. 3)
   if (d->M <= 0 || d->N <= 0 || d->batch <= 0) return SD_OK;
   GemmArgs g = args_from_desc(*d);
   g.ws = workspace;

@@ -234,6 +234,8 @@ __global__ __launch_bounds__(256, 2) void gemm3_mlp_kernel(GemmArgs g, MlpExt e)
   if (POUT) {  // partials (per 64 columns) of every row's sum of squares
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
+      // N = 64 * odd: the last tile's second half lies past N and has no partial (index N / 64 is the next entry's 0)
+      if (bn0 + wc * WN + 64 * p >= g.N) continue;
       float* pout = e.pout + (long)b * e.sPout + (long)((bn0 + wc * WN) / 64 + p) * g.M;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -419,6 +421,8 @@ extern "C" int sd_gemm_bf16x3_mlp(const sd_gemm_desc* d, const sd_mlp_ext* x, sd
     for (int b = 0; b < d->batch; ++b)
       if (b >= SD_MLP_MAXB || !x->norm_w_ptr[b]) return SD_EARG;
   if (pout && d->N % 64) return SD_ESHAPE;
+  // entry b's partials are (N / 64, M) at part_out + b * stride_part_out: a shorter stride overlaps the entries
+  if (pout && d->batch > 1 && x->stride_part_out < (long)(d->N / 64) * d->M) return SD_EARG;
   bool per_entry = false;
   for (int b = 0; b < SD_MLP_MAXB; ++b) {
     if (x->w_rows[b] < 0 || x->w_rows[b] > d->N) return SD_EARG;
@@ -460,7 +464,7 @@ int gemm3_run(const sd_gemm_desc* d, float* workspace, long workspace_floats, fl
 }
 
 extern "C" int sd_gemm_bf16x3(const sd_gemm_desc* d, float* workspace, long workspace_floats, sd_stream stream_) {
-  if (!d || !d->A || !d->B || !d->C) return SD_EARG;
+  if (!d || !d->A || !d->B || !d->C || d->tile > 3) return SD_EARG;
   if (d->M <= 0 || d->N <= 0 || d->batch <= 0) return SD_OK;
   if (d->M < 64 || d->N < 64 || d->K < 64) return sd_gemm_f32(d, workspace, workspace_floats, stream_);
   return gemm3_run(d, workspace, workspace_floats, nullptr, 0, stream_);
@@ -468,7 +472,7 @@ extern "C" int sd_gemm_bf16x3(const sd_gemm_desc* d, float* workspace, long work
 
 extern "C" int sd_gemm_bf16x3_wgrad(const sd_gemm_desc* d, float* workspace, long workspace_floats, float* rowsum,
                                     int accumulate, sd_stream stream_) {
-  if (!d || !d->A || !d->B || !d->C || !rowsum) return SD_EARG;
+  if (!d || !d->A || !d->B || !d->C || !rowsum || d->tile > 3) return SD_EARG;
   if (d->M <= 0 || d->N <= 0) return SD_OK;
   if (d->M < 64 || d->N < 64 || d->K < 64 || d->batch != 1 || d->a_kcontig) return SD_ESHAPE;
   return gemm3_run(d, workspace, workspace_floats, rowsum, accumulate, stream_);
@@ -476,7 +480,7 @@ extern "C" int sd_gemm_bf16x3_wgrad(const sd_gemm_desc* d, float* workspace, lon
 
 extern "C" int sd_gemm_bf16x3_wgrad2(const sd_gemm_desc* d, float* workspace, long workspace_floats, float* rowsum,
                                      float* rowsum2, int rs_split, int accumulate, sd_stream stream_) {
-  if (!d || !d->A || !d->B || !d->C || !rowsum || !rowsum2) return SD_EARG;
+  if (!d || !d->A || !d->B || !d->C || !rowsum || !rowsum2 || d->tile > 3) return SD_EARG;
   if (d->M <= 0 || d->N <= 0) return SD_OK;
   if (d->M < 64 || d->N < 64 || d->K < 64 || d->batch != 1 || d->a_kcontig) return SD_ESHAPE;
   if (rs_split <= 0 || rs_split >= d->M) return SD_ESHAPE;

@@ -1,9 +1,11 @@
 """Bit-identity check between two builds of libsdhip.so (A/B aid): computes the split-bf16 and f32 conv bwd-weight, the
 pooled-gradient bwd-weight on both, the split-bf16 bwd-data, every output of the distribution-head kernels (csrc/dist.hip)
 over the case tables of tests/rowop_models.py, every output of the pool / RMSNorm row entries (csrc/poolnorm.hip) at
-each of their dispatch arms, the fused imagination of the bench agent (random init, seed 0) and the
+each of their dispatch arms, every output of the dense contractions (csrc/gemm.hip, csrc/gemm3.hip: f32, split-bf16, weight
+gradient, MLP and 256-wide MLP entries) over the case tables of tests/gemm_models.py, the fused imagination of the bench agent (random init, seed 0) and the
 parameters after two eager updates of that agent on the bench's synthetic buffer, on fixed inputs, with the library
 SDHIP_LIB points at, and saves them to argv[1]; `python tools/lib_bitcheck.py cmp a.npz b.npz` reports whether every array is bit-identical."""
+import hashlib
 import os
 import sys
 
@@ -74,12 +76,30 @@ def rows(res):
                         res[f"{key}/{k}"] = v.cpu().numpy()
 
 
+def gemms(res):
+    """every output of the float64 tests of the dense contractions, over their full case tables (each dispatch arm):
+    C, the row sums and part_out, as gemm/<family>/<case>/<output>; the N = 64 * odd part_out cases carry "po1" and an
+    odd N / 64 in their names"""
+    import gemm_models as gm
+    import test_gpu_gemm_f64 as t
+    for fam, cases in gm.CASES.items():
+        for c in cases:
+            for k, v in t.run(c)[0].items():
+                if k == "pout_own":
+                    continue
+                v = v.astype(np.float32)
+                if v.size > 1 << 20:  # the 256-wide cases' 50 MB outputs: their SHA-256
+                    v = np.frombuffer(hashlib.sha256(v.tobytes()).digest(), np.uint8)
+                res[f"gemm/{fam}/{c.name}/{k}"] = v
+
+
 def run(out):
     import torch
     from sdreamer import kernels as K
     res = {}
     rowops(res)
     rows(res)
+    gemms(res)
     for ci, co, hw, nb in [(32, 48, 32, 64), (48, 64, 16, 64), (64, 64, 8, 64), (4, 32, 64, 8)]:
         g = torch.Generator().manual_seed(ci * 7 + co)
         x = (torch.rand(nb, hw, hw, ci, generator=g) - 0.5).cuda()
