@@ -803,6 +803,64 @@ int sd_imagine_bwd_ok(const sd_imagine_bwd_desc* d);
 int sd_imagine_bwd_work_floats(const sd_imagine_bwd_desc* d);
 int sd_imagine_bwd(const sd_imagine_bwd_desc* d, sd_stream stream);
 
+/* ---------------------------------------------------------------- fused acting step (Dreamer.act after the encoder)
+ * One environment step of a trained agent on B rows (dreamer.py:330-357): the reset select on the carried state,
+ * RSSM.obs_step (rssm.py:158-178: Deter.forward, obs_net, the posterior's unimix one-hot sample), the actor MLP
+ * (networks.py:313-377) and the action (sampled, or its mode) — 5 + actor_layers kernel launches (8 at the default
+ * three layers; csrc/policy.hip), every contraction exact fp32 (v_mfma_f32_16x16x4_f32; the logits by rows as fp32 dot
+ * products, as in the scan):
+ *   1  k_policy_prelude: the split-K slabs of _dyn_in0 / _dyn_in1 on the reset-selected state, eproj = embed .
+ *      Wo[:, D:]^T + bo, x2 = SiLU(RMSNorm(_dyn_in2(action_norm(prev_action)))), the selected deter, and the transposed
+ *      one-hot half of actor layer 0's weight (rebuilt by every call: no weight image outlives a call);
+ *   2-5  the scan's own step kernels at T = 1: k_hid, k_gate, k_slab (obs_net_0's deter half; its second problem is
+ *      the deter half of actor layer 0), k_logit_rows (logits, sample; its "next step" gather is the one-hot half of
+ *      actor layer 0), so no launch of its own re-reads the new state for the actor;
+ *   then one launch per actor layer 1 .. actor_layers - 1 (the previous layer's slab sum / bias / RMSNorm + SiLU in
+ *      its prologue) and one for the output layer + the action.
+ * Rows with is_first set take zero stoch, deter and prev_action by a select: what the caller left there does not reach
+ * the result. The posterior is sampled in both modes. eval = 0: the action is sampled (bounded normal: tanh(mean) +
+ * eps * scale; one-hot: unimix straight-through); eval = 1: its mode (tanh(mean); the one-hot of the first argmax).
+ * Noise: the posterior's Gumbel noise is Philox stream stream_post, step `step`, element (row + row_offset) * SK + k;
+ * the action's is stream stream_act, step `step`, element (row + row_offset) * A + j; the effective seed is
+ * seed + *seed_ptr, read on the device (graph replay). Every parameter is read in place as f32.
+ * Requirements (else SD_ESHAPE, from sd_policy_step_ok / _work_floats already and before any launch): 1 <= B <= 4096,
+ * U == 256 (the actor's hidden width too), G <= 8, D <= 4096, D/G in {256, 512}, SK in {512, 1024}, Kd in {16, 32},
+ * A >= 1 with A <= 16 (discrete) or 2A <= 32 (continuous), 1 <= actor_layers <= 4, E >= 1 with E % 4 == 0 (the rows of
+ * the (U, D + E) obs_net_0 weight are read as float4s in place). A null required pointer, or an input / weight that is
+ * not 16-byte aligned, on an admitted shape: SD_EARG before any launch. Outputs may not alias inputs or each other.
+ * No allocation, no synchronise, graph-capturable; fixed summation order (two calls on the same inputs give the same
+ * bits). */
+typedef struct sd_policy {
+  int B, D, U, SK, Kd, G, A, E, act_discrete, actor_layers;
+  float eps, unimix, act_unimix, min_std, max_std;
+  int eval;                    /* 0: sample the action, 1: its mode */
+  uint64_t seed;
+  const uint64_t* seed_ptr;    /* optional device seed offset (graph replay) */
+  int step;
+  long row_offset;
+  int stream_post, stream_act;
+  const float *W0, *b0, *n0, *W1, *b1, *n1, *W2, *b2, *n2;  /* _dyn_in0/1/2: (U,D) (U,SK) (U,A), bias and norm (U) */
+  const float *Wh, *bh, *nh;   /* _dyn_hid: (G, D/G, D/G+3U) (D) (D) */
+  const float *Wg, *bg;        /* _dyn_gru: (G, 3D/G, D/G) (3D) */
+  const float *Wo, *bo, *no;   /* obs_net_0: the whole (U, D+E) weight, (U); obs_net_n_0 (U) */
+  const float *Wl, *bl;        /* obs_net_logit: (SK,U) (SK) */
+  const float* Wa[4]; const float* ba[4]; const float* na[4];  /* actor layer i: (U, in_i) (U) (U); in_0 = SK + D */
+  const float *Wao, *bao;      /* actor output: (2A or A, U) rows, bias */
+  /* inputs */
+  const float* embed;          /* (B,E) */
+  const unsigned char* is_first;  /* (B) bytes */
+  const float *stoch, *deter, *prev_action;  /* (B,SK) (B,D) (B,A) */
+  /* outputs */
+  float *stoch_out, *deter_out, *action;     /* (B,SK) (B,D) (B,A) */
+  float *logit, *actor_logit;  /* optional (B,SK), (B, 2A or A): the posterior's / the actor's logits; NULL: not written */
+  float* work;                 /* >= sd_policy_step_work_floats(d) floats */
+} sd_policy;
+/* 1: the shape is admitted, 0: not (no launch, no device access; pointers are not read) */
+int sd_policy_step_ok(const sd_policy* d);
+/* workspace floats; SD_ESHAPE (negative) outside the gate */
+int sd_policy_step_work_floats(const sd_policy* d);
+int sd_policy_step(const sd_policy* d, sd_stream stream);
+
 /* InfoNCE representation loss (dreamer.py:533-542): cross_entropy(logits - rowmax(logits), arange) on an (n, ncol)
  * row-major logits block (ld floats between rows), row r labelled with column r + label_off (data parallel: local
  * rows against the gathered x2 of every rank). fwd writes per-row losses, the row log-sum-exp (saved for bwd) and the

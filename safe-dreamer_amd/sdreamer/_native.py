@@ -77,6 +77,7 @@ def _parse_struct(path, name):
 ScanDesc = _parse_struct(HEADER, "sd_rssm_scan")
 ImagineDesc = _parse_struct(HEADER, "sd_imagine")
 ImagineBwdDesc = _parse_struct(HEADER, "sd_imagine_bwd_desc")
+PolicyDesc = _parse_struct(HEADER, "sd_policy")
 SliceKey = _parse_struct(HEADER, "sd_slice_key")
 
 

@@ -400,6 +400,87 @@ class Dreamer(nn.Module):
             action = self._sample_action(logits, seed, step, 0, STREAM_POLICY_ACT)
         return action, {"stoch": stoch, "deter": deter, "prev_action": action}
 
+    def _fused_policy_ok(self, B):
+        """Shapes csrc/policy.hip admits (sd_policy_step_ok restated from the modules): the intersection of the fused
+        scan's and the fused imagination's actor gate; E % 4: obs_net_0's (U, D + E) rows are read as float4s."""
+        r, a = self.rssm, self.actor
+        if a.mlp._symlog_inputs or a.mlp.out_dim != 256 or r._hidden != 256:
+            return False
+        if a.dist_name not in ("bounded_normal", "onehot"):
+            return False
+        D, G, SK, Kd, A, E = r._deter, r._blocks, r.flat_stoch, r._discrete, self.act_dim, r.embed_size
+        if not 1 <= B <= 4096 or not 1 <= G <= 8 or D % G or D > 4096 or D // G not in (256, 512):
+            return False
+        return SK in (512, 1024) and Kd in (16, 32) and A >= 1 and (A <= 16 if self.act_discrete else 2 * A <= 32) and \
+            1 <= a.mlp.n <= 4 and E >= 1 and E % 4 == 0
+
+    def _policy_desc(self, B):
+        """sd_policy (include/sdhip.h) with the shape, the scalars and every parameter pointer; the caller adds the
+        mode, the noise counters and the buffers. Parameters are read in place: nothing here outlives a call."""
+        r, a = self.rssm, self.actor
+        P = r._p()
+        d = nat.PolicyDesc()
+        d.B, d.D, d.U, d.SK, d.Kd, d.G, d.A, d.E = B, r._deter, r._hidden, r.flat_stoch, r._discrete, r._blocks, \
+            self.act_dim, r.embed_size
+        d.act_discrete, d.actor_layers = int(self.act_discrete), a.mlp.n
+        dist = self.config.actor.dist
+        d.eps, d.unimix = K.EPS, r._unimix_ratio
+        if self.act_discrete:
+            d.act_unimix = float(dist.unimix_ratio)
+        else:
+            d.min_std, d.max_std = float(dist.min_std), float(dist.max_std)
+        for k in ("W0", "b0", "n0", "W1", "b1", "n1", "W2", "b2", "n2", "Wh", "bh", "nh", "Wg", "bg", "Wo", "bo", "no",
+                  "Wl", "bl"):
+            setattr(d, k, P[k].data_ptr())
+        for i, (lin, norm) in enumerate(a.mlp._mods):
+            d.Wa[i], d.ba[i], d.na[i] = lin.weight.data_ptr(), lin.bias.data_ptr(), norm.weight.data_ptr()
+        wo = a.last.weight.contiguous()
+        d.Wao, d.bao = wo.data_ptr(), a.last.bias.data_ptr()
+        return d, (P, wo)
+
+    @torch.no_grad()
+    def policy_step(self, obs, state, eval=False, seed=None, step=0, row_offset=0):
+        """act() with everything after the encoder as one sd_policy_step (csrc/policy.hip: 5 + actor layers fused
+        launches instead of ~29 per-op ones): same arguments, state dict and noise counters as act (row `b` draws as
+        global row `b + row_offset`), results within the fused kernels' tolerance of act's. Shapes outside
+        _fused_policy_ok take act itself and return its bits."""
+        B = obs["is_first"].shape[0]
+        if not self._fused_policy_ok(B):
+            if row_offset:
+                raise ValueError("policy_step: row_offset needs a shape the fused step admits (act draws from row 0)")
+            return self.act(obs, state, eval=eval, seed=seed, step=step)
+        p_obs = self.preprocess(dict(obs))
+        if self._mm:  # as act: the gated embed, the act-side text cache
+            ctx = self.encoder.act_context(p_obs["image"].shape[0], self.device, eval=eval)
+            out = self.encoder({"image": p_obs["image"]}, return_both=True, reuse_text_context=ctx)
+            embed = out[1] if isinstance(out, tuple) else out
+        else:
+            embed = self.encoder({k: v.unsqueeze(1) for k, v in p_obs.items() if k in self.encoder.cnn_shapes
+                                  or k in self.encoder.mlp_shapes})[:, 0]
+        r = self.rssm
+        dev, f32 = embed.device, torch.float32
+        d, _params = self._policy_desc(B)  # (_params: the tensors behind the pointers, alive until the call is issued)
+        d.eval, d.step, d.row_offset = int(bool(eval)), int(step), int(row_offset)
+        d.seed, d.seed_ptr = K.seed_args(self._seed_base + 7 if seed is None else seed)
+        d.stream_post, d.stream_act = STREAM_POLICY, STREAM_POLICY_ACT
+        first = obs["is_first"].reshape(B)
+        first = first.view(torch.uint8) if first.dtype == torch.bool and first.is_contiguous() else \
+            first.to(torch.uint8).contiguous()
+        ins = (embed.contiguous(), first, state["stoch"].reshape(B, -1).contiguous(), state["deter"].contiguous(),
+               state["prev_action"].contiguous())
+        d.embed, d.is_first, d.stoch, d.deter, d.prev_action = (t.data_ptr() for t in ins)
+        stoch = torch.empty(B, r._stoch, r._discrete, dtype=f32, device=dev)
+        deter = torch.empty(B, r._deter, dtype=f32, device=dev)
+        action = torch.empty(B, self.act_dim, dtype=f32, device=dev)
+        d.stoch_out, d.deter_out, d.action = stoch.data_ptr(), deter.data_ptr(), action.data_ptr()
+        nwork = nat.fns["sd_policy_step_work_floats"](ctypes.addressof(d))
+        if nwork < 0:
+            raise nat.NativeError(f"sd_policy_step_work_floats failed with status {nwork}")
+        work = torch.empty(nwork, dtype=f32, device=dev)
+        d.work = work.data_ptr()
+        nat.call("sd_policy_step", ctypes.addressof(d), K.stream())
+        return action, {"stoch": stoch, "deter": deter, "prev_action": action}
+
     def _posterior_text_ctx(self, B, text_index=None):
         """(B, dim) context of text `text_index` (default: the update schedule's current text, the first one before
         any update) in a buffer of its own: neither the update's persistent buffer nor its schedule is touched."""
@@ -484,21 +565,26 @@ class Dreamer(nn.Module):
         error = (model - truth + 1.0) / 2.0
         return torch.cat([truth, model, error], 2)
 
-    def policy_graph(self, B, obs_example, eval=False):
+    def policy_graph(self, B, obs_example, eval=False, fused=False):
         """Dreamer.act for B environments as one replayed HIP graph (latency path).
         Returns policy(obs, state) -> (action, state): copies obs/state into the graph's static inputs, replays, and
         returns views of the graph's static outputs (valid until the next call). Call k samples exactly as
-        act(obs, state, eval, seed=seed_base + k, step=0) does (the per-step seed lives on the device)."""
+        act(obs, state, eval, seed=seed_base + k, step=0) does (the per-step seed lives on the device).
+        fused: capture policy_step (one sd_policy_step after the encoder) instead of act; call k then equals
+        policy_step(obs, state, eval, seed=seed_base + k, step=0)."""
         dev = self.device
+        step_fn = self.policy_step if fused else self.act
         s_obs = {k: torch.zeros_like(v, device=dev) for k, v in obs_example.items()}
         s_state = self.get_initial_state(B)
         seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         if self._mm:  # the act-side context buffer exists before the capture; refreshed eagerly before each replay
             self.encoder.act_context(B, dev, eval=eval)
+        if fused:  # once eagerly: the step kernels raise their dynamic-LDS limit on first use, outside any capture
+            self.policy_step(s_obs, s_state, eval=eval, seed=seed_dev, step=0)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            act, st = self.act(s_obs, s_state, eval=eval, seed=seed_dev, step=0)
+            act, st = step_fn(s_obs, s_state, eval=eval, seed=seed_dev, step=0)
         counter = [0]
         base = self._seed_base + 7
 
